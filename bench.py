@@ -16,10 +16,16 @@ stream (weak scaling — the reference shards streams/polarizations/beams the
 same way) and all-reducing the per-block detection counters.
 
 Usage: python bench.py --gpus N --steps K --warmup W
+                       [--dump-outputs DIR] [--full]
 (For N>1 the driver launches via torch.distributed.run; RANK/LOCAL_RANK/
 WORLD_SIZE/MASTER_* are read from the environment.)
 
-Prints ONE JSON line on rank 0 with the whole-job Msamples/s.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on
+rank 0 with the whole-job Msamples/s.  --dump-outputs DIR additionally writes
+what the last timed step computed (see dump_outputs) so two builds can be
+compared output for output; the inputs are seeded and identical from run to
+run.  --full is reserved for supplementary measurements that need runs of
+their own; the flagship benchmark has none today, so it changes nothing yet.
 """
 
 import argparse
@@ -31,6 +37,57 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+# --dump-outputs keeps the waterfall whole up to this many bytes, else a
+# fixed seeded sample of this size; with the sample's index array of the
+# same size and the ~1 MB time series the whole dump stays under 64 MB
+DUMP_WATERFALL_BYTES = 16 << 20
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(out_dir, eng, last_step):
+    """Write the outputs of the last timed step as out_dir/<name>.npy.
+
+    last_step: [(slot, result)] of the step's blocks in submission order.
+      detect_counts.npy      float64 [blocks, 1 + n_boxcar]: zero_count, then
+                             the detection count of every boxcar length
+      detect_boxcars.npy     float64 [n_boxcar]: the boxcar lengths
+      detect_thresholds.npy  float64 [blocks, n_thresholds]
+      time_series.npy        float32 [ts_count]: last block, whole
+      waterfall.npy          float32 [K, 2] (re, im): last block's dedispersed
+                             waterfall, whole (row-major) if it fits
+                             DUMP_WATERFALL_BYTES, else the elements listed in
+      waterfall_index.npy    float64 [K]: flat indices of the seeded sample
+    """
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a, dtype):
+        np.save(os.path.join(out_dir, name + ".npy"),
+                np.ascontiguousarray(a, dtype=dtype))
+
+    save("detect_counts",
+         [[r["zero_count"]] + [c for _, c in r["counts"]]
+          for _, r in last_step], np.float64)
+    save("detect_boxcars", [b for b, _ in last_step[-1][1]["counts"]],
+         np.float64)
+    save("detect_thresholds", [list(r["thresholds"]) for _, r in last_step],
+         np.float64)
+
+    # device buffers of the last block's slot are intact: nothing was
+    # submitted after it and the engine is synchronized
+    slot = last_step[-1][0]
+    save("time_series", eng.time_series(slot).cpu().numpy(), np.float32)
+    wf = torch.view_as_real(eng.waterfall(slot)).reshape(-1, 2)
+    k = DUMP_WATERFALL_BYTES // 8
+    if wf.shape[0] > k:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(
+            0, wf.shape[0], k))
+        save("waterfall_index", idx, np.float64)
+        wf = wf[torch.from_numpy(idx).to(wf.device)]
+    save("waterfall", wf.cpu().numpy(), np.float32)
 
 
 def main():
@@ -70,6 +127,14 @@ def main():
                     help="torch.distributed backend for world>1 (nccl=RCCL "
                     "over xGMI, one rank per GPU; gloo validates the "
                     "distributed path with several ranks sharing one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's "
+                    "outputs (detection counters, time series, waterfall "
+                    "sample) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run supplementary measurements beyond the "
+                    "headline figure (none exist yet; a plain run is "
+                    "already lean)")
     args = ap.parse_args()
 
     import torch
@@ -164,17 +229,29 @@ def main():
                 pending_handles[b].wait()
                 pending_handles[b] = None
 
+    # (slot, result) of every block of the current run_steps call, in
+    # submission order — what a caller of the engine receives per block
+    results = []
+
     def run_steps(k):
         # keep ALL slots in flight (submit-ahead depth = n_slots); waiting
         # with only one block queued leaves the GPU idle during the host-side
         # stat aggregation (~20% measured on the J1644 config)
+        results.clear()
         inflight = []
+
+        def collect():
+            slot = inflight.pop(0)
+            res = eng.wait(slot)
+            agg(res)
+            results.append((slot, res))
+
         for i in range(k * args.blocks_per_step):
             inflight.append(eng.submit(pinned[i % len(pinned)]))
             if len(inflight) >= args.slots:
-                agg(eng.wait(inflight.pop(0)))
+                collect()
         while inflight:
-            agg(eng.wait(inflight.pop(0)))
+            collect()
         drain_handles()
         eng.synchronize()
 
@@ -245,6 +322,9 @@ def main():
             },
         }
         print(json.dumps(out), flush=True)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, results[-args.blocks_per_step:])
 
     if distributed:
         torch.distributed.destroy_process_group()

@@ -22,7 +22,10 @@ def _dist_worker(rank, world, port, fn_name):
     os.environ["MASTER_PORT"] = str(port)
     os.environ["WORLD_SIZE"] = str(world)
     os.environ["RANK"] = str(rank)
-    os.environ["LOCAL_RANK"] = str(rank)
+    # gloo/CPU test: where GPUs are visible init_distributed also binds the
+    # rank to device LOCAL_RANK, so both ranks share device 0 rather than
+    # require one GPU per rank
+    os.environ["LOCAL_RANK"] = "0"
     from srtb_amd.parallel.sharding import (DetectionAggregator,
                                             broadcast_config,
                                             init_distributed)
