@@ -388,6 +388,69 @@ torch::Tensor t_native_fft(torch::Tensor x, int64_t sign) {
   return out;
 }
 
+// Batched backward NativeFft with the fused RFI + zap + dedispersion pre-op
+// on its first pass, below engine level.  One plan runs once per entry of
+// `dms` (the DM-sweep front end's usage); returns ([out per dm], [whether the
+// column-polynomial phase path ran per dm]).
+std::tuple<std::vector<torch::Tensor>, std::vector<bool>> t_preop_backward_fft(
+    torch::Tensor spec, int64_t maxcol_log2, int64_t final_log2, double f_min,
+    double f_c, double df, std::vector<double> dms,
+    std::vector<std::vector<int64_t>> ranges, bool enable_rfi,
+    double threshold, int64_t channel_count) {
+  CHECK_CUDA(spec);
+  CHECK_CONTIG(spec);
+  TORCH_CHECK(spec.scalar_type() == torch::kComplexFloat);
+  TORCH_CHECK(ranges.size() <= 16, "at most 16 zap ranges");
+  const size_t len = spec.size(-1);
+  const size_t n = spec.numel();
+  const size_t batch = n / len;
+  auto stream = cur_stream();
+  NativeFft plan;
+  plan.plan(len, batch, +1, stream, (int)maxcol_log2, (int)final_log2);
+  TORCH_CHECK(plan.first_pass_fusable(), "plan has no column first pass");
+  torch::Tensor mean;
+  FftPreop pre;
+  if (enable_rfi) {
+    mean = t_mean_power(spec);
+    pre.mean_power = mean.data_ptr<double>();
+    pre.threshold = (float)threshold;
+    pre.norm_coeff =
+        (float)std::pow((double)n * (double)n / (double)channel_count, -0.5);
+  }
+  pre.n_zap = (int)ranges.size();
+  for (size_t i = 0; i < ranges.size(); ++i) {
+    pre.zap[i].lo = (unsigned long long)ranges[i][0];
+    pre.zap[i].hi = (unsigned long long)ranges[i][1];
+  }
+  pre.f_min = f_min;
+  pre.f_c = f_c;
+  pre.df = df;
+  std::vector<torch::Tensor> outs;
+  std::vector<bool> poly;
+  for (double dm : dms) {
+    pre.dm = dm;
+    poly.push_back(plan.preop_uses_poly(pre));
+    auto work = spec.clone();  // the column passes run in place
+    auto out = torch::empty_like(spec);
+    plan.exec(cptr(work), cptr(out), stream, &pre);
+    outs.push_back(out);
+  }
+  check(hipStreamSynchronize(stream), "preop_backward_fft sync");
+  return {outs, poly};
+}
+
+torch::Tensor t_dedisp_poly_factors(int64_t nc, int64_t n, int64_t stride,
+                                    double f_min, double f_c, double df,
+                                    double dm, torch::Device dev) {
+  auto out = torch::empty({nc}, torch::TensorOptions()
+                                    .dtype(torch::kComplexFloat)
+                                    .device(dev));
+  check(dedisp_poly_factors(cptr(out), (size_t)nc, (uint32_t)n,
+                            (size_t)stride, f_min, f_c, df, dm, cur_stream()),
+        "dedisp_poly_factors");
+  return out;
+}
+
 torch::Tensor t_native_rfft(torch::Tensor x) {
   // real forward via packed-complex trick + r2c post; returns n/2 bins
   CHECK_CUDA(x);
@@ -657,6 +720,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("correlate", &t_correlate);
   m.def("native_fft", &t_native_fft, py::arg("x"), py::arg("sign"));
   m.def("native_rfft", &t_native_rfft, py::arg("x"));
+  m.def("preop_backward_fft", &t_preop_backward_fft, py::arg("spec"),
+        py::arg("maxcol_log2"), py::arg("final_log2"), py::arg("f_min"),
+        py::arg("f_c"), py::arg("df"), py::arg("dms"),
+        py::arg("ranges") = std::vector<std::vector<int64_t>>{},
+        py::arg("enable_rfi") = false, py::arg("threshold") = 0.0,
+        py::arg("channel_count") = 1);
+  m.def("dedisp_poly_factors", &t_dedisp_poly_factors);
   m.def("bench_fft", &t_bench_fft, py::arg("len"), py::arg("batch"),
         py::arg("sign"), py::arg("iters") = 20, py::arg("backend") = "native");
   m.def("bench_rfft", &t_bench_rfft, py::arg("n"), py::arg("iters") = 20,

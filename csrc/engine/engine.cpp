@@ -115,6 +115,8 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
     // 2^29-class packed C2C always favors the native plan; the batched
     // backward favors rocFFT below the measured l_ = 2^17 crossover
     fused_unpack_off_ = std::getenv("SRTB_NO_FUSED_UNPACK") != nullptr;
+    if (const char* sc = std::getenv("SRTB_SERIAL_CHAINS"))
+      serial_chains_ = std::atoi(sc) != 0 ? 1 : 0;
     const int be = cfg.fft_backend;
     native_fft_ = (be == 0 || be == 2) && NativeFft::supported(nc_);
     native_bwd_ = native_fft_ && NativeFft::supported(l_) &&
@@ -125,9 +127,10 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
       if (native_bwd_) {
         // the RFI+dedispersion preop fuses into the backward's FIRST
         // pass; SRTB_FFT_BWD32=1 plans it 32-max-column + final-256 (the
-        // pair32 kernel runs the fp64 phase at 6 waves/SIMD).  A/B on one
-        // box decides the default — kernel-sum favors pair32 (28.1 vs
-        // 28.7 ms/block) but wall favored the wide plan on another box.
+        // pair32 kernel hid more of the per-bin fp64 phase at 6
+        // waves/SIMD: kernel-sum favored pair32, 28.1 vs 28.7 ms/block,
+        // wall favored the wide plan).  The column-polynomial phase
+        // removes that VALU cost, see docs/fft_design.md.
         const char* b32 = std::getenv("SRTB_FFT_BWD32");
         if (b32 && std::atoi(b32) != 0)
           s.nbwd.plan(l_, s_, +1, s.stream, /*maxcol_log2=*/5,
@@ -148,8 +151,10 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
       // mean comes from Parseval on the packed spectrum — the standalone
       // 8.6 GB r2c pass disappears.  MEASURED SLOWER end-to-end (50.8 vs
       // 61.5 Gsps, r02): the combine adds a second 4.3 GB read + sincos
-      // to the pass that is already the chain's critical kernel (fp64
-      // dedispersion), and the lost overlap outweighs the traffic saved.
+      // to the pass that was then the chain's critical kernel (per-bin
+      // fp64 dedispersion), and the lost overlap outweighs the traffic
+      // saved.  Not re-measured with the column-polynomial phase, which
+      // this mode does not use (fft_col_preop_uses_poly).
       // Kept opt-in; numerics are exact (57 GPU tests pass either way).
       {
         const char* fe = std::getenv("SRTB_FUSE_R2C");
@@ -238,6 +243,37 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
     throw std::runtime_error("dm override requires use_phase_table=false");
 
   RoctxRange r_chain("srtb_block_chain");
+  const bool fr2c = fuse_r2c_;  // r2c pair-combine fused into bwd load
+  // RFI s1 + manual zap + dedispersion fuse into the backward FFT's first
+  // column pass when the native planner allows it (step 4.+5. below)
+  const bool fuse_into_bwd = native_bwd_ && s.nbwd.first_pass_fusable();
+  FftPreop pre;
+  if (fuse_into_bwd) {
+    pre.mean_power = cfg_.enable_rfi_s1 ? s.mean_power : nullptr;
+    pre.threshold = cfg_.rfi_threshold;
+    pre.norm_coeff = norm_coeff_;
+    pre.n_zap = cfg_.n_zap_ranges;
+    for (int i = 0; i < cfg_.n_zap_ranges; ++i) pre.zap[i] = cfg_.zap_ranges[i];
+    pre.f_min = f_min_;
+    pre.f_c = f_c_;
+    pre.df = df_;
+    pre.dm = dm;
+    pre.table = table;
+    pre.r2c_m = fr2c ? nc_ : 0;
+  }
+  // Slot scheduling.  With the per-bin fp64 dedispersion phase the fused
+  // backward pass is VALU-bound and overlaps well with the other slot's
+  // memory-bound passes, so the slots' chains run concurrently.  With the
+  // column-polynomial phase every pass of the chain is memory-bound:
+  // concurrent chains only share HBM (each pass takes twice as long), run in
+  // lockstep and then issue their H2D copies together with the GPU idle
+  // (measured: 20 % idle, 20.6 vs 16.9 ms per block).  So this chain's
+  // kernels wait for the previously enqueued chain; the H2D copy enqueued
+  // before it still overlaps that chain.  Not inside a graph capture.
+  if (record_event && last_chain_done_ && last_chain_done_ != s.done &&
+      (serial_chains_ > 0 ||
+       (serial_chains_ < 0 && fuse_into_bwd && s.nbwd.preop_uses_poly(pre))))
+    check_hip(hipStreamWaitEvent(st, last_chain_done_, 0), "chain order");
   const float* fft_in = s.samples;
   // fused unpack: for the 2-bit rectangular-window native-forward case the
   // FFT's first column pass decodes the raw bytes itself (0.25 GB of byte
@@ -262,7 +298,6 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
   } else if (!dev_raw) {
     fft_in = dev_samples;
   }
-  const bool fr2c = fuse_r2c_;  // r2c pair-combine fused into bwd load
   if (native_fft_ && fr2c) {
     // 2. forward C2C of the packed-real view; the DIF store accumulates
     //    per-WG sum|Z|^2 and the RFI mean comes from Parseval — the
@@ -298,20 +333,7 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
   // first column pass when the native planner allows it (saves a full
   // read+write of the 4 GB spectrum); otherwise the standalone fused kernel.
   float2* wf;
-  const bool fuse_into_bwd = native_bwd_ && s.nbwd.first_pass_fusable();
   if (fuse_into_bwd) {
-    FftPreop pre;
-    pre.mean_power = cfg_.enable_rfi_s1 ? s.mean_power : nullptr;
-    pre.threshold = cfg_.rfi_threshold;
-    pre.norm_coeff = norm_coeff_;
-    pre.n_zap = cfg_.n_zap_ranges;
-    for (int i = 0; i < cfg_.n_zap_ranges; ++i) pre.zap[i] = cfg_.zap_ranges[i];
-    pre.f_min = f_min_;
-    pre.f_c = f_c_;
-    pre.df = df_;
-    pre.dm = dm;
-    pre.table = table;
-    pre.r2c_m = fr2c ? nc_ : 0;
     s.nbwd.exec(s.spec, reinterpret_cast<float2*>(s.samples), st, &pre,
                 watfft_window_ ? nullptr : s.sk_dif_partials, nullptr, 2,
                 fr2c ? s.xbuf : nullptr);
@@ -393,6 +415,7 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
   if (record_event) {
     check_hip(hipEventRecord(s.done, st), "event record");
     s.busy = true;
+    last_chain_done_ = s.done;
   }
 }
 

@@ -193,6 +193,10 @@ class PipelineEngine {
   };
   std::vector<std::unique_ptr<Slot>> slots_;
   int next_slot_ = 0;
+  // `done` event of the most recently enqueued chain (any slot): the next
+  // chain waits on it when chains are serialized, see enqueue_chain()
+  hipEvent_t last_chain_done_ = nullptr;
+  int serial_chains_ = -1;  // SRTB_SERIAL_CHAINS: -1 auto, 0 never, 1 always
 };
 
 }  // namespace srtb_hip

@@ -55,10 +55,13 @@ class NativeFft {
   // Plan a batched C2C: `batch` rows of length `len`, contiguous.
   // maxcol_log2_ovr / final_log2_ovr (0 = policy default) override the
   // factorization defaults for THIS plan — the engine plans its backward
-  // (preop-fused) FFT with 32-max columns + final 256: the fp64
-  // dedispersion fused into the first pass wants the 6-wave/SIMD pair32
-  // kernel, not the 4-wave pair64 (r02 bench profile: 8.96 vs 4.56
-  // ms/block contended).  Explicit SRTB_FFT_* env still wins.
+  // (preop-fused) FFT with 32-max columns + final 256 under
+  // SRTB_FFT_BWD32=1.  That shape was introduced when the per-bin fp64
+  // dedispersion phase made the fused first pass VALU-bound (r02 bench
+  // profile: 8.96 vs 4.56 ms/block contended) and the 6-wave/SIMD pair32
+  // kernel hid more of it than pair64; with the column-polynomial phase
+  // (fft_col_preop_uses_poly) that VALU cost is gone, see
+  // docs/fft_design.md.  Explicit SRTB_FFT_* env still wins.
   void plan(size_t len, size_t batch, int sign, hipStream_t stream,
             int maxcol_log2_ovr = 0, int final_log2_ovr = 0) {
     destroy();
@@ -255,6 +258,14 @@ class NativeFft {
   // first pass when that pass is a register column pass.
   bool first_pass_fusable() const {
     return !passes_.empty() && passes_[0].kind == PassKind::kCol;
+  }
+
+  // Whether exec() with this pre-op takes the column-polynomial
+  // dedispersion path (decided per call: it depends on preop.dm).
+  bool preop_uses_poly(const FftPreop& preop) const {
+    return first_pass_fusable() &&
+           fft_col_preop_uses_poly(passes_[0].d, passes_[0].n_ffts, sign_,
+                                   preop);
   }
 
   // SK-stat accumulation can fuse into the final DIF pass when each

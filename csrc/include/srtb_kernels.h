@@ -219,8 +219,11 @@ struct FftPreop {
   ZapRange zap[16] = {};
   double f_min = 0, f_c = 0, df = 0, dm = 0;
   // optional cached dedispersion factors [nc]; when set the pass reads the
-  // table (one extra coalesced float2 load) instead of the fp64 phase
-  // computation, which would otherwise double the pass's VALU cost
+  // table (one extra coalesced float2 load) instead of computing the phase.
+  // Only of interest where the column-polynomial phase (below) does not
+  // apply: that one costs ~10 integer VALU instructions per bin and no
+  // extra traffic, whereas the per-bin fp64 formula triples the pass's VALU
+  // count and the table adds a 4.3 GB read (measured slower than either)
   const float2* table = nullptr;
   // != 0: the pass input is the PACKED forward spectrum Z (length r2c_m);
   // the r2c pair-combine X[k] = E + w_k O runs at load (eliminates the
@@ -248,6 +251,22 @@ hipError_t fft_col_pass(const float2* in, float2* out, const FftPassDesc& d,
                         const float2* tw_hi, const float2* tw_lo,
                         hipStream_t stream, const FftPreop* preop = nullptr,
                         const uint8_t* raw2 = nullptr, int raw_bits = 2);
+
+// Whether fft_col_pass evaluates this pre-op's dedispersion phase as a
+// per-column cubic in wrapping fixed point (csrc/kernels/common.h) instead
+// of the per-bin fp64 formula.  True when the cubic's truncation bound
+//   D*1e6*|dm| / f^5 * (df*stride*(n-1))^4   (f = smallest |f| of the band)
+// is <= 2^-28 turns for THIS dm, no table / r2c mode is set, the pass is the
+// backward (sign > 0) twiddled one, and SRTB_DEDISP_POLY is not 0.
+bool fft_col_preop_uses_poly(const FftPassDesc& d, size_t n_ffts, int sign,
+                             const FftPreop& preop);
+
+// Test surface: out[b] = the factor the polynomial pre-op applies at bin b
+// of an nc-bin spectrum laid out as columns of (n, stride), n in {2..64}
+// pow2, nc a multiple of n*stride.
+hipError_t dedisp_poly_factors(float2* out, size_t nc, uint32_t n,
+                               size_t stride, double f_min, double f_c,
+                               double df, double dm, hipStream_t stream);
 
 // Final composite pass: in-place radix-4 DIF in LDS with base-4
 // digit-reversal folded into the store, plus multi-digit output scatter.

@@ -80,4 +80,55 @@ __device__ inline float2 srtb_dedisp_factor(size_t i, double f_min,
   return make_float2(c, s);
 }
 
+// Column-polynomial form of the same factor for the bins of one FFT column,
+// f_j = f0 + j*delta (f0 = f_min + df*bin0, delta = df*stride).  The turn
+// count k(f) = A (f-f_c)^2 / f, A = D*1e6*dm/f_c^2, expands about f0 as
+//   k(f_j) = c0 + c1 j + c2 j^2 + c3 j^3 + O(A f_c^2 delta^4 j^4 / f0^5)
+// with, writing q = D*1e6*dm/f0, r = (f0-f_c)/f_c, u = delta/f0:
+//   c0 = q r^2   c1 = q r (r+2) u   c2 = q u^2   c3 = -q u^3
+// (no cancellation in any coefficient).  Only frac(k) matters, so each
+// coefficient's fraction is held as a 64-bit fixed-point turn count and the
+// cubic is combined in wrapping integer arithmetic: the ~1e6-turn integer
+// parts vanish exactly and no per-bin fp64 division, modf or range reduction
+// is left.  The caller (fft_col_pass) checks the truncation bound on the host
+// and falls back to srtb_dedisp_factor when it does not hold.
+struct DedispPoly {
+  unsigned long long c0, c1, c2, c3;  // frac(c_p) * 2^64
+};
+
+__device__ inline unsigned long long srtb_turns_to_fix64(double t) {
+  const double fr = t - floor(t);  // [0, 1]; 1.0 only for tiny negative t
+  return fr < 1.0 ? (unsigned long long)(fr * 18446744073709551616.0) : 0ull;
+}
+
+// per-thread set-up: three fp64 divisions for a whole column
+__device__ inline DedispPoly srtb_dedisp_poly_setup(unsigned long long bin0,
+                                                    unsigned long long stride,
+                                                    double f_min, double f_c,
+                                                    double df, double dm) {
+  const double f0 = f_min + df * (double)bin0;
+  const double r = (f0 - f_c) / f_c;
+  const double q = (kDispersionConstantMHz * 1e6) * dm / f0;
+  const double u = df * (double)stride / f0;
+  DedispPoly p;
+  p.c0 = srtb_turns_to_fix64(q * (r * r));  // srtb_dedisp_factor's k at bin0
+  p.c1 = srtb_turns_to_fix64(q * r * (r + 2.0) * u);
+  p.c2 = srtb_turns_to_fix64(q * (u * u));
+  p.c3 = srtb_turns_to_fix64(-q * (u * u) * u);
+  return p;
+}
+
+// exp(-2 pi i frac(k(f_j))); j must be a compile-time constant at the call
+// site (fully unrolled loops) so the integer multiplies fold to immediates.
+// The top 32 bits of the wrapped sum are a signed turn count in [-0.5, 0.5),
+// which the hardware sine/cosine take directly (their argument is in turns).
+__device__ __forceinline__ float2 srtb_dedisp_poly_eval(const DedispPoly& p,
+                                                        unsigned j) {
+  const unsigned long long jj = j;
+  const unsigned long long t = p.c0 + jj * (p.c1 + jj * (p.c2 + jj * p.c3));
+  const float turns = (float)(int)(unsigned)(t >> 32) * 0x1p-32f;
+  return make_float2(__builtin_amdgcn_cosf(turns),
+                     -__builtin_amdgcn_sinf(turns));
+}
+
 }  // namespace srtb_hip

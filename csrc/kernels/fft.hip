@@ -27,6 +27,7 @@
 //    strided passes instances are q0-consecutive so a row of F elements is
 //    contiguous in HBM.
 
+#include <cmath>
 #include <cstdlib>
 #include "common.h"
 #include "../include/srtb_kernels.h"
@@ -464,7 +465,72 @@ __device__ inline float2 r2c_combine_load(const float2* __restrict__ zbase,
   return make_float2(even.x + wo.x, even.y + wo.y);
 }
 
-template <int N, bool TWIDDLE, int SIGN, bool PREOP, int DEC = 0>
+// fused rfi_dedisperse at a column pass's load (spectrum.hip
+// k_rfi_dedisp_fused semantics) with the per-bin fp64 phase, the cached
+// table or the r2c pair-combine, all selected at run time
+__device__ __forceinline__ float2 preop_apply(const float2* __restrict__ in,
+                                              float2 x,
+                                              unsigned long long flat,
+                                              const FftPreopDev& pre,
+                                              float thr_mean) {
+  if (pre.r2c_m) x = r2c_combine_load(in, x, flat, pre.r2c_m);
+  bool zap = pre.mean_power && (norm2(x) > thr_mean);
+  for (int z = 0; z < pre.n_zap; ++z)
+    zap |= (flat >= pre.zap[z].lo) & (flat <= pre.zap[z].hi);
+  if (zap) return make_float2(0.f, 0.f);
+  if (pre.mean_power) {
+    x.x *= pre.norm_coeff;
+    x.y *= pre.norm_coeff;
+  }
+  return cmulf(x, pre.table ? pre.table[flat]
+                            : srtb_dedisp_factor(flat, pre.f_min, pre.f_c,
+                                                 pre.df, pre.dm));
+}
+
+// Pre-op of the POLY instances: same zap / normalize / rotate semantics as
+// above with the dedispersion factor from the column polynomial (common.h),
+// and every runtime-uniform test hoisted out of the per-element path so the
+// unrolled load loop is straight-line code (all loads issue up front, as in
+// the plain instances):
+//  - mean_power is folded into thr / nc by the caller (thr = +inf, nc = 1
+//    without RFI stage 1: never zaps, and x * 1 is exact);
+//  - the manual zap ranges become one per-thread bit mask, built before the
+//    loads and skipped for threads whose column meets no range;
+//  - the table / r2c modes do not exist here — fft_col_pass launches these
+//    instances only when both are off.
+// flat_of(r) = spectrum bin of the thread's r-th element, all of them in
+// [first, last].
+template <int R, typename FlatFn>
+__device__ __forceinline__ uint32_t preop_zap_mask(const FftPreopDev& pre,
+                                                   unsigned long long first,
+                                                   unsigned long long last,
+                                                   FlatFn flat_of) {
+  static_assert(R <= 32, "one mask bit per register element");
+  uint32_t mask = 0;
+  for (int z = 0; z < pre.n_zap; ++z) {
+    const unsigned long long lo = pre.zap[z].lo, hi = pre.zap[z].hi;
+    if (hi < first || lo > last) continue;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const unsigned long long flat = flat_of(r);
+      mask |= (uint32_t)((flat >= lo) & (flat <= hi)) << r;
+    }
+  }
+  return mask;
+}
+
+__device__ __forceinline__ float2 preop_poly_apply(float2 x, bool zap_bit,
+                                                   float thr, float nc,
+                                                   const DedispPoly& poly,
+                                                   unsigned j) {
+  const bool zap = zap_bit | (norm2(x) > thr);
+  const float2 y = cmulf(make_float2(x.x * nc, x.y * nc),
+                         srtb_dedisp_poly_eval(poly, j));
+  return zap ? make_float2(0.f, 0.f) : y;
+}
+
+template <int N, bool TWIDDLE, int SIGN, bool PREOP, int DEC = 0,
+          bool POLY = false>
 __global__ void __launch_bounds__(256)
     k_fft_col(const float2* __restrict__ in, float2* __restrict__ out,
               FftPassDescDev d, unsigned long long n_ffts,
@@ -480,8 +546,20 @@ __global__ void __launch_bounds__(256)
   digits(id, d, q0, q1, q2);
   const unsigned long long base = q0 * d.in_c0 + q1 * d.in_c1 + q2 * d.in_c2;
   float thr_mean = 0.f;
+  [[maybe_unused]] float norm_c = 1.f;
+  [[maybe_unused]] DedispPoly poly{};
+  [[maybe_unused]] uint32_t zap_mask = 0;
   if constexpr (PREOP) {
     if (pre.mean_power) thr_mean = pre.threshold * (float)(*pre.mean_power);
+    if constexpr (POLY) {
+      if (pre.mean_power) norm_c = pre.norm_coeff;
+      else thr_mean = __builtin_inff();
+      poly = srtb_dedisp_poly_setup(base, d.in_stride, pre.f_min, pre.f_c,
+                                    pre.df, pre.dm);
+      zap_mask = preop_zap_mask<N>(
+          pre, base, base + (N - 1) * d.in_stride,
+          [&](int i) { return base + (unsigned)i * d.in_stride; });
+    }
   }
   float2 v[N];
   // a column spans (N-1)*stride < L <= 2^29 elements, so 32-bit offsets
@@ -496,22 +574,12 @@ __global__ void __launch_bounds__(256)
     if constexpr (DEC != 0) x = decN_load<DEC>(raw2, flat);
     else x = ld_stream(colbase + off, d.tuning);
     if constexpr (PREOP) {
-      // fused rfi_dedisperse (spectrum.hip k_rfi_dedisp_fused semantics);
       // `flat` IS the spectrum bin index for in-place column passes
-      if (pre.r2c_m) x = r2c_combine_load(in, x, flat, pre.r2c_m);
-      bool zap = pre.mean_power && (norm2(x) > thr_mean);
-      for (int z = 0; z < pre.n_zap; ++z)
-        zap |= (flat >= pre.zap[z].lo) & (flat <= pre.zap[z].hi);
-      if (zap) {
-        x = make_float2(0.f, 0.f);
+      if constexpr (POLY) {
+        x = preop_poly_apply(x, (zap_mask >> i) & 1u, thr_mean, norm_c, poly,
+                             i);
       } else {
-        if (pre.mean_power) {
-          x.x *= pre.norm_coeff;
-          x.y *= pre.norm_coeff;
-        }
-        x = cmulf(x, pre.table ? pre.table[flat]
-                               : srtb_dedisp_factor(flat, pre.f_min, pre.f_c,
-                                                    pre.df, pre.dm));
+        x = preop_apply(in, x, flat, pre, thr_mean);
       }
     }
     v[col_sigma<N>(i)] = x;
@@ -553,7 +621,8 @@ __device__ inline float2 shfl_xor1(float2 x) {
   return make_float2(__shfl_xor(x.x, 1, 64), __shfl_xor(x.y, 1, 64));
 }
 
-template <bool TWIDDLE, int SIGN, bool PREOP, int DEC = 0>
+template <bool TWIDDLE, int SIGN, bool PREOP, int DEC = 0,
+          bool POLY = false>
 __global__ void __launch_bounds__(256)
     k_fft_col_pair64(const float2* __restrict__ in, float2* __restrict__ out,
                      FftPassDescDev d, unsigned long long n_ffts,
@@ -571,8 +640,24 @@ __global__ void __launch_bounds__(256)
   digits(id, d, q0, q1, q2);
   const unsigned long long base = q0 * d.in_c0 + q1 * d.in_c1 + q2 * d.in_c2;
   float thr_mean = 0.f;
+  [[maybe_unused]] float norm_c = 1.f;
+  [[maybe_unused]] DedispPoly poly{};
+  [[maybe_unused]] uint32_t zap_mask = 0;
   if constexpr (PREOP) {
     if (pre.mean_power) thr_mean = pre.threshold * (float)(*pre.mean_power);
+    if constexpr (POLY) {
+      if (pre.mean_power) norm_c = pre.norm_coeff;
+      else thr_mean = __builtin_inff();
+      // σ⁻¹(32 + r) = σ⁻¹(r) + 2: lane p expands about its own first element
+      // so the polynomial index is the compile-time sigma^-1(r) on both lanes
+      const unsigned long long first = base + 2ull * p * d.in_stride;
+      poly = srtb_dedisp_poly_setup(first, d.in_stride, pre.f_min, pre.f_c,
+                                    pre.df, pre.dm);
+      zap_mask = preop_zap_mask<32>(
+          pre, first, first + 61 * d.in_stride, [&](int r) {
+            return first + (unsigned)col_sigma_inv64(r) * d.in_stride;
+          });
+    }
   }
   float2 v[32];
   const float2* __restrict__ colbase = in + base;
@@ -588,20 +673,11 @@ __global__ void __launch_bounds__(256)
     else x = ld_stream(colbase + off, d.tuning);
     if constexpr (PREOP) {
       const unsigned long long flat = base + off;
-      if (pre.r2c_m) x = r2c_combine_load(in, x, flat, pre.r2c_m);
-      bool zap = pre.mean_power && (norm2(x) > thr_mean);
-      for (int z = 0; z < pre.n_zap; ++z)
-        zap |= (flat >= pre.zap[z].lo) & (flat <= pre.zap[z].hi);
-      if (zap) {
-        x = make_float2(0.f, 0.f);
+      if constexpr (POLY) {
+        x = preop_poly_apply(x, (zap_mask >> r) & 1u, thr_mean, norm_c, poly,
+                             col_sigma_inv64(r));
       } else {
-        if (pre.mean_power) {
-          x.x *= pre.norm_coeff;
-          x.y *= pre.norm_coeff;
-        }
-        x = cmulf(x, pre.table ? pre.table[flat]
-                               : srtb_dedisp_factor(flat, pre.f_min, pre.f_c,
-                                                    pre.df, pre.dm));
+        x = preop_apply(in, x, flat, pre, thr_mean);
       }
     }
     v[r] = x;
@@ -651,8 +727,8 @@ __global__ void __launch_bounds__(256)
 // lane-local, the final radix-2 stage (L=32) exchanges halves with one
 // shfl_xor(…,1) per butterfly.  16 data registers per lane → higher
 // occupancy than the mono col<32> kernel (~143 VGPRs, 3 waves/SIMD),
-// which matters most for the VALU-heavy fused-preop (fp64 dedispersion)
-// backward pass.
+// which mattered most for the fused pre-op backward pass while its per-bin
+// fp64 dedispersion phase was VALU-bound (the POLY instances are not).
 // ---------------------------------------------------------------------------
 
 constexpr int col_sigma_inv32(int pos) {
@@ -661,7 +737,8 @@ constexpr int col_sigma_inv32(int pos) {
   return 0;
 }
 
-template <bool TWIDDLE, int SIGN, bool PREOP, int DEC = 0>
+template <bool TWIDDLE, int SIGN, bool PREOP, int DEC = 0,
+          bool POLY = false>
 __global__ void __launch_bounds__(256)
     k_fft_col_pair32(const float2* __restrict__ in, float2* __restrict__ out,
                      FftPassDescDev d, unsigned long long n_ffts,
@@ -679,8 +756,24 @@ __global__ void __launch_bounds__(256)
   digits(id, d, q0, q1, q2);
   const unsigned long long base = q0 * d.in_c0 + q1 * d.in_c1 + q2 * d.in_c2;
   float thr_mean = 0.f;
+  [[maybe_unused]] float norm_c = 1.f;
+  [[maybe_unused]] DedispPoly poly{};
+  [[maybe_unused]] uint32_t zap_mask = 0;
   if constexpr (PREOP) {
     if (pre.mean_power) thr_mean = pre.threshold * (float)(*pre.mean_power);
+    if constexpr (POLY) {
+      if (pre.mean_power) norm_c = pre.norm_coeff;
+      else thr_mean = __builtin_inff();
+      // σ⁻¹(16 + r) = σ⁻¹(r) + 1: lane p expands about its own first element
+      // so the polynomial index is the compile-time sigma^-1(r) on both lanes
+      const unsigned long long first = base + 1ull * p * d.in_stride;
+      poly = srtb_dedisp_poly_setup(first, d.in_stride, pre.f_min, pre.f_c,
+                                    pre.df, pre.dm);
+      zap_mask = preop_zap_mask<16>(
+          pre, first, first + 30 * d.in_stride, [&](int r) {
+            return first + (unsigned)col_sigma_inv32(r) * d.in_stride;
+          });
+    }
   }
   float2 v[16];
   const float2* __restrict__ colbase = in + base;
@@ -694,20 +787,11 @@ __global__ void __launch_bounds__(256)
     else x = ld_stream(colbase + off, d.tuning);
     if constexpr (PREOP) {
       const unsigned long long flat = base + off;
-      if (pre.r2c_m) x = r2c_combine_load(in, x, flat, pre.r2c_m);
-      bool zap = pre.mean_power && (norm2(x) > thr_mean);
-      for (int z = 0; z < pre.n_zap; ++z)
-        zap |= (flat >= pre.zap[z].lo) & (flat <= pre.zap[z].hi);
-      if (zap) {
-        x = make_float2(0.f, 0.f);
+      if constexpr (POLY) {
+        x = preop_poly_apply(x, (zap_mask >> r) & 1u, thr_mean, norm_c, poly,
+                             col_sigma_inv32(r));
       } else {
-        if (pre.mean_power) {
-          x.x *= pre.norm_coeff;
-          x.y *= pre.norm_coeff;
-        }
-        x = cmulf(x, pre.table ? pre.table[flat]
-                               : srtb_dedisp_factor(flat, pre.f_min, pre.f_c,
-                                                    pre.df, pre.dm));
+        x = preop_apply(in, x, flat, pre, thr_mean);
       }
     }
     v[r] = x;
@@ -1342,6 +1426,84 @@ hipError_t fft_stockham_pass(const float2* in, float2* out,
 }
 
 
+// SRTB_DEDISP_POLY=0 forces the per-bin fp64 phase (A/B runs).  Read per
+// call, not cached: it only matters on the pre-op pass (once per block), and
+// the DM-sweep front end already re-decides per submit.
+static bool dedisp_poly_enabled() {
+  const char* e = std::getenv("SRTB_DEDISP_POLY");
+  return e ? (std::atoi(e) != 0) : true;
+}
+
+bool fft_col_preop_uses_poly(const FftPassDesc& hd, size_t n_ffts, int sign,
+                             const FftPreop& preop) {
+  if (!dedisp_poly_enabled()) return false;
+  if (preop.table || preop.r2c_m) return false;
+  // instantiated for the backward twiddled column pass only — the one place
+  // the planner puts a pre-op
+  if (sign <= 0 || hd.tw_mod == 0) return false;
+  if (hd.n < 2 || hd.n > 64) return false;
+  // Lagrange remainder of the cubic: (4th derivative of k)/4! * span^4,
+  // where that derivative/4! = D*1e6*dm / f^5 is largest at the band's
+  // smallest |f|
+  const double f_a = preop.f_min;
+  const double f_b =
+      preop.f_min + preop.df * (double)(n_ffts * (size_t)hd.n - 1);
+  if (!(f_a * f_b > 0.0)) return false;  // band touches or crosses 0
+  const double f_lo = std::fmin(std::fabs(f_a), std::fabs(f_b));
+  const double span =
+      std::fabs(preop.df) * (double)hd.in_stride * (double)(hd.n - 1);
+  const double x = span / f_lo;
+  const double bound =
+      std::fabs(kDispersionConstantMHz * 1e6 * preop.dm) / f_lo * (x * x) *
+      (x * x);
+  return bound <= 0x1p-28;  // turns; false for NaN
+}
+
+namespace {
+// test surface: the factor the POLY pre-op applies at every bin of a
+// spectrum laid out as columns of (N, stride)
+template <int N>
+__global__ void k_dedisp_poly_factors(float2* __restrict__ out,
+                                      unsigned long long n_cols,
+                                      unsigned long long stride, double f_min,
+                                      double f_c, double df, double dm) {
+  const unsigned long long id =
+      (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= n_cols) return;
+  const unsigned long long base = (id / stride) * (N * stride) + id % stride;
+  const DedispPoly poly =
+      srtb_dedisp_poly_setup(base, stride, f_min, f_c, df, dm);
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    out[base + (unsigned long long)j * stride] =
+        srtb_dedisp_poly_eval(poly, j);
+}
+}  // namespace
+
+hipError_t dedisp_poly_factors(float2* out, size_t nc, uint32_t n,
+                               size_t stride, double f_min, double f_c,
+                               double df, double dm, hipStream_t stream) {
+  if (stride == 0 || nc == 0 || nc % ((size_t)n * stride) != 0)
+    return hipErrorInvalidValue;
+  const size_t n_cols = nc / n;
+  const dim3 grid((uint32_t)((n_cols + 255) / 256));
+#define POLYF_CASE(NN)                                                       \
+  case NN:                                                                   \
+    hipLaunchKernelGGL((k_dedisp_poly_factors<NN>), grid, dim3(256), 0,      \
+                       stream, out, (unsigned long long)n_cols,              \
+                       (unsigned long long)stride, f_min, f_c, df, dm);      \
+    break;
+  switch (n) {
+    POLYF_CASE(2) POLYF_CASE(4) POLYF_CASE(8) POLYF_CASE(16) POLYF_CASE(32)
+    POLYF_CASE(64)
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef POLYF_CASE
+  SRTB_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
 hipError_t fft_col_pass(const float2* in, float2* out, const FftPassDesc& hd,
                         size_t n_ffts, int sign, const float2* tw_n,
                         const float2* tw_hi, const float2* tw_lo,
@@ -1365,6 +1527,10 @@ hipError_t fft_col_pass(const float2* in, float2* out, const FftPassDesc& hd,
     pre.table = preop->table;
     pre.r2c_m = preop->r2c_m;
   }
+  // column-polynomial dedispersion phase when its truncation bound holds
+  // for THIS launch's dm; otherwise the per-bin fp64 instances below
+  const bool poly =
+      preop && !raw2 && fft_col_preop_uses_poly(hd, n_ffts, sign, *preop);
   FftPassDescDev d;
   d.n = hd.n;
   d.n_log2 = ilog2(hd.n);
@@ -1406,9 +1572,15 @@ hipError_t fft_col_pass(const float2* in, float2* out, const FftPassDesc& hd,
                              else COL_LAUNCH_D(N, 1, 16); }                  \
   else { if (sign < 0) COL_LAUNCH_D(N, -1, -16);                             \
          else COL_LAUNCH_D(N, 1, -16); }
+#define COL_LAUNCH_POLY(N)                                                   \
+  hipLaunchKernelGGL((k_fft_col<N, true, 1, true, 0, true>), dim3(grid),     \
+                     dim3(256), 0, stream, in, out, d, n_ffts, tw_n, tw_hi,  \
+                     tw_lo, pre, raw2)
 #define COL_DISPATCH(N)                                                      \
   case N:                                                                    \
-    if (raw2) {                                                              \
+    if (poly) {                                                              \
+      COL_LAUNCH_POLY(N);                                                    \
+    } else if (raw2) {                                                       \
       COL_DISPATCH_D(N)                                                      \
     } else if (twiddle) {                                                           \
       if (sign < 0) { if (preop) COL_LAUNCH(N, true, -1, true);              \
@@ -1449,6 +1621,15 @@ hipError_t fft_col_pass(const float2* in, float2* out, const FftPassDesc& hd,
     // neutral vs the mono kernel (3 waves) and is opt-in via
     // SRTB_FFT_PAIR32=1 pending more soak coverage; mono is the default.
     case 32:
+      if (poly) {
+        if (use_pair32())
+          hipLaunchKernelGGL((k_fft_col_pair32<true, 1, true, 0, true>),
+                             dim3(grid2), dim3(256), 0, stream, in, out, d,
+                             n_ffts, tw_n, tw_hi, tw_lo, pre, raw2);
+        else
+          COL_LAUNCH_POLY(32);
+        break;
+      }
       if (use_pair32()) {
         if (raw2) {
           if (raw_bits == 1) { if (sign < 0) COL_LAUNCH_P32D(-1, 1);
@@ -1497,6 +1678,12 @@ hipError_t fft_col_pass(const float2* in, float2* out, const FftPassDesc& hd,
       }
       break;
     case 64:
+      if (poly) {
+        hipLaunchKernelGGL((k_fft_col_pair64<true, 1, true, 0, true>),
+                           dim3(grid2), dim3(256), 0, stream, in, out, d,
+                           n_ffts, tw_n, tw_hi, tw_lo, pre, raw2);
+        break;
+      }
       if (raw2) {
         if (raw_bits == 1) { if (sign < 0) COL_LAUNCH_PD(-1, 1);
                              else COL_LAUNCH_PD(1, 1); }
@@ -1533,6 +1720,7 @@ hipError_t fft_col_pass(const float2* in, float2* out, const FftPassDesc& hd,
 #undef COL_DISPATCH_D
 #undef COL_LAUNCH
 #undef COL_LAUNCH_D
+#undef COL_LAUNCH_POLY
 #undef COL_LAUNCH_P
 #undef COL_LAUNCH_PD
 #undef COL_LAUNCH_P32
