@@ -180,6 +180,9 @@ struct Config {
   double baseband_sample_rate = 1e9;
   bool baseband_reserve_sample = true;
   double dm = 0.0;
+  // DM-trial search: every block is searched at each of these DMs from one
+  // forward spectrum (empty = single-DM operation at `dm`)
+  std::vector<double> dm_trial_list;
   std::vector<std::string> udp_receiver_address = {"10.0.1.2"};
   std::vector<int> udp_receiver_port = {12004};
   std::vector<int> udp_receiver_cpu_preferred = {0};
@@ -240,7 +243,10 @@ inline void Config::assign(const std::string& key, const std::string& raw0) {
   else if (key == "baseband_sample_rate") baseband_sample_rate = D();
   else if (key == "baseband_reserve_sample") baseband_reserve_sample = B();
   else if (key == "dm") dm = D();
-  else if (key == "udp_receiver_address") udp_receiver_address = split_list(raw);
+  else if (key == "dm_trial_list") {
+    dm_trial_list.clear();
+    for (auto& p : split_list(raw)) dm_trial_list.push_back(Expr::eval(p));
+  } else if (key == "udp_receiver_address") udp_receiver_address = split_list(raw);
   else if (key == "udp_receiver_port") {
     udp_receiver_port.clear();
     for (auto& p : split_list(raw))
@@ -335,6 +341,12 @@ inline std::string Config::dump() const {
     << "baseband_output_file_prefix = " << baseband_output_file_prefix
     << "\n"
     << "log_level = " << log_level << "\n";
+  if (!dm_trial_list.empty()) {
+    o << "dm_trial_list = ";
+    for (size_t i = 0; i < dm_trial_list.size(); ++i)
+      o << (i ? "," : "") << dm_trial_list[i];
+    o << "\n";
+  }
   return o.str();
 }
 

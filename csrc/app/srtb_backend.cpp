@@ -42,12 +42,12 @@ using srtb_hip::PipelineEngine;
 namespace {
 
 // reference coherent_dedispersion.hpp:87-128 (Python twin: ref.nsamps_reserved)
-size_t nsamps_reserved(const Config& c) {
+size_t nsamps_reserved(const Config& c, double dm) {
   if (!c.baseband_reserve_sample) return 0;
   const double f = c.baseband_freq_low + c.baseband_bandwidth;
   const double fc = c.baseband_freq_low;
   const double delay =
-      -4.148808e3 * c.dm * (1.0 / (f * f) - 1.0 / (fc * fc));
+      -4.148808e3 * dm * (1.0 / (f * f) - 1.0 / (fc * fc));
   const long long minimal =
       2 * (long long)std::llround(delay * c.baseband_sample_rate);
   const long long per_bin = 2 * (long long)c.spectrum_channel_count;
@@ -174,7 +174,26 @@ int main(int argc, char** argv) {
   const int n_streams =
       (fmt_name == "naocpsr_snap1" || fmt_name == "gznupsr_a1") ? 2 : 1;
 
-  const size_t reserved_ref = nsamps_reserved(cfg);
+  // DM-trial search (dm_trial_list): every block runs one forward half and
+  // one backward half per trial DM (PipelineEngine::submit_trials)
+  const std::vector<double>& trial_dms = cfg.dm_trial_list;
+  const bool trial_mode = !trial_dms.empty();
+  if (trial_mode && n_streams > 1) {
+    SRTB_APP_LOGE("config: dm_trial_list needs a single-stream format, "
+                  << fmt_name << " carries " << n_streams << " streams");
+    return 2;
+  }
+  if (trial_mode && (int)trial_dms.size() > srtb_hip::kMaxDmTrials) {
+    SRTB_APP_LOGE("config: dm_trial_list holds " << trial_dms.size()
+                  << " trials, at most " << srtb_hip::kMaxDmTrials);
+    return 2;
+  }
+  // the overlap must cover the most dispersed trial
+  double reserve_dm = cfg.dm;
+  for (const double d : trial_dms)
+    if (std::fabs(d) > std::fabs(reserve_dm)) reserve_dm = d;
+
+  const size_t reserved_ref = nsamps_reserved(cfg, reserve_dm);
   size_t reserved = reserved_ref;
   const bool udp_mode = cfg.input_file_path.empty();
   if (udp_mode && reserved > 0) {
@@ -218,6 +237,7 @@ int main(int argc, char** argv) {
   ec.snr_threshold = (float)cfg.signal_detect_signal_noise_threshold;
   ec.max_boxcar_length = cfg.signal_detect_max_boxcar_length;
   ec.nsamps_reserved = reserved;
+  ec.max_dm_trials = (int)trial_dms.size();
   parse_zap_ranges(cfg, ec);
 
   // multi-GPU: one process per GPU (torchrun or shell-loop launched); the
@@ -236,6 +256,10 @@ int main(int argc, char** argv) {
                                    << " dm=" << cfg.dm
                                    << " reserved=" << reserved
                                    << " streams=" << n_streams);
+  if (trial_mode)
+    SRTB_APP_LOGI("dm-trials: " << trial_dms.size()
+                                << " trials per block, nsamps_reserved="
+                                << reserved << " for dm=" << reserve_dm);
 
   std::vector<std::unique_ptr<PipelineEngine>> engines;
   for (int i = 0; i < n_streams; ++i)
@@ -460,6 +484,11 @@ int main(int argc, char** argv) {
 
   auto submit_block = [&](int bi) -> std::array<int, 2> {
     std::array<int, 2> slots{-1, -1};
+    if (trial_mode) {
+      slots[0] = engine.submit_trials(bufs[bi], raw_bytes, trial_dms.data(),
+                                      (int)trial_dms.size());
+      return slots;
+    }
     if (n_streams == 1) {
       slots[0] = engine.submit(bufs[bi], raw_bytes);
       return slots;
@@ -557,8 +586,44 @@ int main(int argc, char** argv) {
     const InFlight w = inflight.front();
     inflight.erase(inflight.begin());
     std::vector<srtb_hip::BlockResult> res(n_streams);
-    for (int si = 0; si < n_streams; ++si)
-      res[si] = engines[si]->wait(w.slots[si]);
+    // DM-trial search: the block's stream result is that of its best trial
+    // (positive trials first, then peak S/N), found before the gate below
+    std::vector<srtb_hip::TrialResult> trials;
+    std::vector<float> trial_snr;
+    std::vector<unsigned> trial_box, trial_idx;
+    int best_trial = -1;
+    bool best_positive = false;
+    if (trial_mode) {
+      trials = engine.wait_trials(w.slots[0]);
+      for (size_t k = 0; k < trials.size(); ++k) {
+        const srtb_hip::TrialResult& t = trials[k];
+        const srtb_hip::TrialPeak* pk = &t.peaks.front();
+        for (const auto& p : t.peaks)
+          if (p.snr > pk->snr) pk = &p;
+        trial_snr.push_back(pk->snr);
+        trial_box.push_back(pk->boxcar_length);
+        trial_idx.push_back(pk->index);
+        uint64_t pos = 0;
+        for (auto& [len, cnt] : t.result.counts) pos += cnt;
+        const bool positive =
+            pos > 0 && t.result.zero_count <
+                           cfg.signal_detect_channel_threshold * (double)S;
+        if (best_trial < 0 || (positive && !best_positive) ||
+            (positive == best_positive && pk->snr > trial_snr[best_trial])) {
+          best_trial = (int)k;
+          best_positive = positive;
+        }
+      }
+      res[0] = trials[best_trial].result;
+      SRTB_APP_LOGI("dm-trials block " << w.counter << " best_dm="
+                    << trials[best_trial].dm << " snr="
+                    << trial_snr[best_trial] << " boxcar="
+                    << trial_box[best_trial] << " sample="
+                    << trial_idx[best_trial]);
+    } else {
+      for (int si = 0; si < n_streams; ++si)
+        res[si] = engines[si]->wait(w.slots[si]);
+    }
     ++blocks;
     if (write_all_fd >= 0) {
       // record-everything tail: append the valid region and release the
@@ -582,6 +647,8 @@ int main(int argc, char** argv) {
       bool any = false;
       for (int si = 0; si < n_streams; ++si)
         for (auto& [len, cnt] : res[si].counts) any |= cnt > 0;
+      for (const auto& t : trials)
+        for (auto& [len, cnt] : t.result.counts) any |= cnt > 0;
       if (any) ++detections;
       return;
     }
@@ -611,6 +678,26 @@ int main(int argc, char** argv) {
         SRTB_APP_LOGI("detection in block " << w.counter << " stream " << si
                                             << " (" << pos
                                             << " samples over threshold)");
+        if (trial_mode) {
+          // make the best positive trial the slot's current one; its re-run
+          // is ordered before the dump's D2H copies on the same stream
+          engine.select_trial(w.slots[0], best_trial);
+          // sidecar: one text row per trial
+          std::ostringstream rows;
+          for (size_t k = 0; k < trials.size(); ++k) {
+            uint64_t over = 0;
+            for (auto& [len, cnt] : trials[k].result.counts) over += cnt;
+            rows << trials[k].dm << " " << trial_snr[k] << " " << trial_box[k]
+                 << " " << trial_idx[k] << " " << over << " "
+                 << trials[k].result.zero_count << "\n";
+          }
+          const std::string path =
+              out_prefix + std::to_string(w.counter) + ".dmt";
+          writers.post([path, text = rows.str()] {
+            std::ofstream f(path);
+            f << text;
+          });
+        }
         dump_stream(si, w.slots[si], res[si], w.counter);
       }
       recent_positive.push_back(w.counter);

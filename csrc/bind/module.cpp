@@ -155,10 +155,22 @@ void t_rfi_dedisperse_fused(torch::Tensor spec, bool enable_rfi,
                             double threshold, int64_t channel_count,
                             std::vector<std::vector<int64_t>> ranges,
                             double f_min, double f_c, double df, double dm,
-                            c10::optional<torch::Tensor> table) {
+                            c10::optional<torch::Tensor> table,
+                            c10::optional<torch::Tensor> out) {
   CHECK_CUDA(spec);
   CHECK_CONTIG(spec);
   const size_t n = spec.numel();
+  // out= (optional): write the result there and leave spec untouched;
+  // out aliasing spec is the in-place call
+  float2* dst = cptr(spec);
+  if (out.has_value()) {
+    CHECK_CUDA(*out);
+    CHECK_CONTIG(*out);
+    TORCH_CHECK(out->scalar_type() == spec.scalar_type() &&
+                    (size_t)out->numel() == n,
+                "out must match spec in dtype and size");
+    dst = cptr(*out);
+  }
   torch::Tensor mean;
   const double* mp = nullptr;
   if (enable_rfi) {
@@ -175,10 +187,43 @@ void t_rfi_dedisperse_fused(torch::Tensor spec, bool enable_rfi,
   }
   const float2* tb = nullptr;
   if (table.has_value()) tb = cptr(*table);
-  check(rfi_dedisperse_fused(cptr(spec), n, mp, (float)threshold, coeff, zr,
+  check(rfi_dedisperse_fused(static_cast<const float2*>(cptr(spec)), dst, n,
+                             mp, (float)threshold, coeff, zr,
                              (int)ranges.size(), f_min, f_c, df, dm, tb,
                              cur_stream()),
         "rfi_dedisperse_fused");
+}
+
+// (values, indices) of the raw-series peak and of every boxcar length's
+std::vector<torch::Tensor> t_detect_peaks(torch::Tensor ts,
+                                          torch::Tensor cumsum,
+                                          std::vector<int64_t> lengths) {
+  CHECK_CUDA(ts);
+  CHECK_CONTIG(ts);
+  CHECK_CUDA(cumsum);
+  CHECK_CONTIG(cumsum);
+  TORCH_CHECK(ts.scalar_type() == torch::kFloat32 &&
+              cumsum.scalar_type() == torch::kFloat32);
+  TORCH_CHECK(lengths.empty() || cumsum.numel() == ts.numel(),
+              "cumsum must have ts's length");
+  TORCH_CHECK(lengths.size() <= 12, "at most 12 boxcar lengths");
+  std::vector<size_t> ls;
+  for (int64_t L : lengths) {
+    TORCH_CHECK(L > 0, "boxcar lengths must be positive");
+    ls.push_back((size_t)L);
+  }
+  const int64_t n_out = 1 + (int64_t)ls.size();
+  auto scratch = torch::empty({(int64_t)detect_peaks_scratch_bytes()},
+                              ts.options().dtype(torch::kUInt8));
+  auto values = torch::empty({n_out}, ts.options());
+  auto indices = torch::empty({n_out}, ts.options().dtype(torch::kInt32));
+  check(detect_peaks(ts.data_ptr<float>(), cumsum.data_ptr<float>(),
+                     ts.numel(), ls.data(), (int)ls.size(),
+                     scratch.data_ptr(), values.data_ptr<float>(),
+                     reinterpret_cast<unsigned*>(indices.data_ptr<int32_t>()),
+                     cur_stream()),
+        "detect_peaks");
+  return {values, indices.to(torch::kInt64)};
 }
 
 torch::Tensor t_sk_row_stats(torch::Tensor wf) {
@@ -569,7 +614,8 @@ class PyEngine {
            int64_t max_boxcar, int64_t nsamps_reserved,
            std::vector<std::vector<int64_t>> zap_ranges, bool use_phase_table,
            bool enable_rfi_s1, bool enable_sk, int64_t n_slots,
-           int64_t fft_backend, int64_t window_kind, bool use_hip_graph) {
+           int64_t fft_backend, int64_t window_kind, bool use_hip_graph,
+           int64_t max_dm_trials) {
     EngineConfig c;
     c.baseband_input_count = n;
     c.baseband_input_bits = (int)nbits;
@@ -595,6 +641,7 @@ class PyEngine {
     c.fft_backend = (int)fft_backend;
     c.window_kind = (int)window_kind;
     c.use_hip_graph = use_hip_graph;
+    c.max_dm_trials = (int)max_dm_trials;
     eng_ = std::make_unique<PipelineEngine>(c, (int)n_slots);
   }
 
@@ -627,8 +674,28 @@ class PyEngine {
                                        producer_event());
   }
 
-  py::dict wait(int64_t slot) {
-    auto r = eng_->wait((int)slot);
+  int64_t submit_trials(torch::Tensor raw, std::vector<double> dms) {
+    TORCH_CHECK(raw.is_contiguous());
+    TORCH_CHECK((size_t)raw.numel() * raw.element_size() == eng_->raw_bytes(),
+                "raw block has wrong byte size");
+    if (raw.is_cuda())
+      return eng_->submit_trials_device(raw.data_ptr(), eng_->raw_bytes(),
+                                        dms.data(), (int)dms.size(),
+                                        producer_event());
+    return eng_->submit_trials(raw.data_ptr(), eng_->raw_bytes(), dms.data(),
+                               (int)dms.size());
+  }
+
+  int64_t submit_trials_samples(torch::Tensor samples,
+                                std::vector<double> dms) {
+    TORCH_CHECK(samples.is_cuda() && samples.is_contiguous());
+    TORCH_CHECK(samples.scalar_type() == torch::kFloat32);
+    return eng_->submit_trials_samples_device(
+        samples.data_ptr<float>(), samples.numel(), dms.data(),
+        (int)dms.size(), producer_event());
+  }
+
+  static py::dict result_dict(const BlockResult& r) {
     py::dict d;
     d["zero_count"] = r.zero_count;
     py::list counts;
@@ -638,6 +705,53 @@ class PyEngine {
     for (float t : r.thresholds) thr.append(t);
     d["thresholds"] = thr;
     return d;
+  }
+
+  py::dict wait(int64_t slot) { return result_dict(eng_->wait((int)slot)); }
+
+  // one dict per trial: wait()'s keys plus "dm" and "peaks", a list of
+  // {boxcar_length, value, index, snr} (raw series first)
+  py::list wait_trials(int64_t slot) {
+    py::list out;
+    for (const auto& t : eng_->wait_trials((int)slot)) {
+      py::dict d = result_dict(t.result);
+      d["dm"] = t.dm;
+      py::list peaks;
+      for (const auto& p : t.peaks) {
+        py::dict pd;
+        pd["boxcar_length"] = p.boxcar_length;
+        pd["value"] = p.value;
+        pd["index"] = p.index;
+        pd["snr"] = p.snr;
+        peaks.append(pd);
+      }
+      d["peaks"] = peaks;
+      out.append(d);
+    }
+    return out;
+  }
+
+  // blocks until the re-run has finished
+  void select_trial(int64_t slot, int64_t k) {
+    eng_->select_trial((int)slot, (int)k);
+    check(hipStreamSynchronize(eng_->stream((int)slot)), "select_trial sync");
+  }
+
+  torch::Tensor dm_time_plane(int64_t slot) {
+    return torch::from_blob(eng_->dm_time_plane_ptr((int)slot),
+                            {(int64_t)eng_->n_trials((int)slot),
+                             (int64_t)eng_->ts_count()},
+                            torch::TensorOptions()
+                                .dtype(torch::kFloat32)
+                                .device(torch::kCUDA));
+  }
+
+  torch::Tensor cumsum(int64_t slot) {
+    return torch::from_blob(eng_->cumsum_ptr((int)slot),
+                            {(int64_t)eng_->ts_count()},
+                            torch::TensorOptions()
+                                .dtype(torch::kFloat32)
+                                .device(torch::kCUDA));
   }
 
   void synchronize() { eng_->synchronize(); }
@@ -702,7 +816,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rfi_dedisperse_fused", &t_rfi_dedisperse_fused, py::arg("spec"),
         py::arg("enable_rfi"), py::arg("threshold"), py::arg("channel_count"),
         py::arg("ranges"), py::arg("f_min"), py::arg("f_c"), py::arg("df"),
-        py::arg("dm"), py::arg("table") = c10::nullopt);
+        py::arg("dm"), py::arg("table") = c10::nullopt,
+        py::arg("out") = c10::nullopt);
+  m.def("detect_peaks", &t_detect_peaks, py::arg("ts"), py::arg("cumsum"),
+        py::arg("lengths"));
   m.def("sk_row_stats", &t_sk_row_stats);
   m.def("sk_mitigate", &t_sk_mitigate);
   m.def("sk_v1_mitigate", &t_sk_v1_mitigate, py::arg("wf"),
@@ -736,7 +853,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def(py::init<int64_t, int64_t, int64_t, double, double, double, double,
                     double, double, double, int64_t, int64_t,
                     std::vector<std::vector<int64_t>>, bool, bool, bool,
-                    int64_t, int64_t, int64_t, bool>(),
+                    int64_t, int64_t, int64_t, bool, int64_t>(),
            py::arg("n"), py::arg("nbits"), py::arg("channels"),
            py::arg("freq_low"), py::arg("bandwidth"), py::arg("sample_rate"),
            py::arg("dm"), py::arg("rfi_threshold") = 10.0,
@@ -746,12 +863,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("use_phase_table") = false,
            py::arg("enable_rfi_s1") = true, py::arg("enable_sk") = true,
            py::arg("n_slots") = 2, py::arg("fft_backend") = 2,
-           py::arg("window_kind") = 0, py::arg("use_hip_graph") = false)
+           py::arg("window_kind") = 0, py::arg("use_hip_graph") = false,
+           py::arg("max_dm_trials") = 0)
       .def("submit", &PyEngine::submit, py::arg("raw"),
            py::arg("dm_override") = std::nan(""))
       .def("submit_samples", &PyEngine::submit_samples, py::arg("samples"),
            py::arg("dm_override") = std::nan(""))
       .def("wait", &PyEngine::wait)
+      .def("submit_trials", &PyEngine::submit_trials, py::arg("raw"),
+           py::arg("dms"))
+      .def("submit_trials_samples", &PyEngine::submit_trials_samples,
+           py::arg("samples"), py::arg("dms"))
+      .def("wait_trials", &PyEngine::wait_trials)
+      .def("select_trial", &PyEngine::select_trial)
+      .def("dm_time_plane", &PyEngine::dm_time_plane)
+      .def("cumsum", &PyEngine::cumsum)
       .def("synchronize", &PyEngine::synchronize)
       .def("waterfall", &PyEngine::waterfall)
       .def("time_series", &PyEngine::time_series)

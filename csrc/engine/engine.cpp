@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
+#include <string>
 
 namespace srtb_hip {
 
@@ -72,6 +73,10 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
   f_c_ = cfg.freq_low + cfg.bandwidth;
   df_ = cfg.bandwidth / (double)nc_;
 
+  if (cfg.max_dm_trials < 0 || cfg.max_dm_trials > kMaxDmTrials)
+    throw std::runtime_error("max_dm_trials must be in [0, " +
+                             std::to_string(kMaxDmTrials) + "]");
+
   const int np = reduce_partials();
   for (int i = 0; i < n_slots_; ++i) slots_.emplace_back(new Slot());
   for (auto& sp : slots_) {
@@ -111,6 +116,31 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
               "pinned cnt");
     check_hip(hipHostMalloc(&s.h_thresholds, (1 + n_boxcars_) * sizeof(float)),
               "pinned thr");
+    s.last_row = plain_row(s);
+    if (const size_t T = (size_t)cfg.max_dm_trials) {
+      const size_t nthr = 1 + (size_t)n_boxcars_;
+      check_hip(hipMalloc(&s.trial_w, nc_ * sizeof(float2)), "trial w alloc");
+      check_hip(hipMalloc(&s.trial_plane, T * ts_count_ * sizeof(float)),
+                "trial plane alloc");
+      check_hip(hipMalloc(&s.trial_counters, T * ncnt * sizeof(unsigned)),
+                "trial cnt alloc");
+      check_hip(hipMalloc(&s.trial_thresholds, T * nthr * sizeof(float)),
+                "trial thr alloc");
+      check_hip(hipMalloc(&s.trial_peak_val, T * nthr * sizeof(float)),
+                "trial peak alloc");
+      check_hip(hipMalloc(&s.trial_peak_idx, T * nthr * sizeof(unsigned)),
+                "trial peak idx alloc");
+      check_hip(hipHostMalloc(&s.h_trial_counters, T * ncnt * sizeof(unsigned)),
+                "pinned trial cnt");
+      check_hip(hipHostMalloc(&s.h_trial_thresholds, T * nthr * sizeof(float)),
+                "pinned trial thr");
+      check_hip(hipHostMalloc(&s.h_trial_peak_val, T * nthr * sizeof(float)),
+                "pinned trial peak");
+      check_hip(hipHostMalloc(&s.h_trial_peak_idx, T * nthr * sizeof(unsigned)),
+                "pinned trial peak idx");
+      check_hip(hipMalloc(&s.peak_scratch, detect_peaks_scratch_bytes()),
+                "peak scratch alloc");
+    }
     // backend selection (see EngineConfig::fft_backend): the forward
     // 2^29-class packed C2C always favors the native plan; the batched
     // backward favors rocFFT below the measured l_ = 2^17 crossover
@@ -224,6 +254,19 @@ PipelineEngine::~PipelineEngine() {
     (void)hipFree(s.thresholds);
     (void)hipHostFree(s.h_counters);
     (void)hipHostFree(s.h_thresholds);
+    if (s.trial_w) {
+      (void)hipFree(s.trial_w);
+      (void)hipFree(s.trial_plane);
+      (void)hipFree(s.trial_counters);
+      (void)hipFree(s.trial_thresholds);
+      (void)hipFree(s.trial_peak_val);
+      (void)hipFree(s.trial_peak_idx);
+      (void)hipHostFree(s.h_trial_counters);
+      (void)hipHostFree(s.h_trial_thresholds);
+      (void)hipHostFree(s.h_trial_peak_val);
+      (void)hipHostFree(s.h_trial_peak_idx);
+      (void)hipFree(s.peak_scratch);
+    }
     if (s.graph_exec) (void)hipGraphExecDestroy(s.graph_exec);
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -233,22 +276,11 @@ PipelineEngine::~PipelineEngine() {
   if (watfft_window_) (void)hipFree(watfft_window_);
 }
 
-void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
-                                   const float* dev_samples, double dm,
-                                   bool record_event) {
-  hipStream_t st = s.stream;
-  if (std::isnan(dm)) dm = cfg_.dm;
-  const float2* table = phase_table_;
-  if (table && dm != cfg_.dm)
-    throw std::runtime_error("dm override requires use_phase_table=false");
-
-  RoctxRange r_chain("srtb_block_chain");
-  const bool fr2c = fuse_r2c_;  // r2c pair-combine fused into bwd load
-  // RFI s1 + manual zap + dedispersion fuse into the backward FFT's first
-  // column pass when the native planner allows it (step 4.+5. below)
-  const bool fuse_into_bwd = native_bwd_ && s.nbwd.first_pass_fusable();
+// The pre-op of the backward FFT's fused first pass (RFI s1 + manual zap +
+// dedispersion at `dm`); meaningful only when that pass is fusable.
+FftPreop PipelineEngine::make_preop(const Slot& s, double dm) const {
   FftPreop pre;
-  if (fuse_into_bwd) {
+  if (native_bwd_ && s.nbwd.first_pass_fusable()) {
     pre.mean_power = cfg_.enable_rfi_s1 ? s.mean_power : nullptr;
     pre.threshold = cfg_.rfi_threshold;
     pre.norm_coeff = norm_coeff_;
@@ -258,9 +290,54 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
     pre.f_c = f_c_;
     pre.df = df_;
     pre.dm = dm;
-    pre.table = table;
-    pre.r2c_m = fr2c ? nc_ : 0;
+    pre.table = phase_table_;
+    pre.r2c_m = fuse_r2c_ ? nc_ : 0;
   }
+  return pre;
+}
+
+PipelineEngine::ResultRow PipelineEngine::plain_row(Slot& s) const {
+  return ResultRow{s.counters, s.thresholds, s.h_counters, s.h_thresholds};
+}
+
+PipelineEngine::ResultRow PipelineEngine::trial_row(Slot& s, int k) const {
+  const size_t ncnt = 2 + (size_t)n_boxcars_, nthr = 1 + (size_t)n_boxcars_;
+  return ResultRow{s.trial_counters + k * ncnt, s.trial_thresholds + k * nthr,
+                   s.h_trial_counters + k * ncnt,
+                   s.h_trial_thresholds + k * nthr};
+}
+
+// The per-block chain: the forward half (steps 1-3, independent of the DM)
+// and the backward half (steps 4-11) in one go, in place on the slot's
+// spectrum.  A DM-trial submission (enqueue_trials) runs the same two halves
+// as one front and many backs.
+void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
+                                   const float* dev_samples, double dm,
+                                   bool record_event) {
+  if (std::isnan(dm)) dm = cfg_.dm;
+  if (phase_table_ && dm != cfg_.dm)
+    throw std::runtime_error("dm override requires use_phase_table=false");
+
+  RoctxRange r_chain("srtb_block_chain");
+  if (record_event) {
+    const bool fuse_into_bwd = native_bwd_ && s.nbwd.first_pass_fusable();
+    order_after_last_chain(
+        s, fuse_into_bwd && serial_chains_ < 0 &&
+               s.nbwd.preop_uses_poly(make_preop(s, dm)));
+  }
+  enqueue_front(s, dev_raw, dev_samples);
+  enqueue_back(s, dm, plain_row(s), /*ts_dst=*/nullptr,
+               /*keep_spectrum=*/false);
+  s.trial_dms.clear();
+  s.cur_trial = -1;
+  if (record_event) {
+    check_hip(hipEventRecord(s.done, s.stream), "event record");
+    s.busy = true;
+    last_chain_done_ = s.done;
+  }
+}
+
+void PipelineEngine::order_after_last_chain(Slot& s, bool uses_poly) {
   // Slot scheduling.  With the per-bin fp64 dedispersion phase the fused
   // backward pass is VALU-bound and overlaps well with the other slot's
   // memory-bound passes, so the slots' chains run concurrently.  With the
@@ -270,10 +347,23 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
   // (measured: 20 % idle, 20.6 vs 16.9 ms per block).  So this chain's
   // kernels wait for the previously enqueued chain; the H2D copy enqueued
   // before it still overlaps that chain.  Not inside a graph capture.
-  if (record_event && last_chain_done_ && last_chain_done_ != s.done &&
-      (serial_chains_ > 0 ||
-       (serial_chains_ < 0 && fuse_into_bwd && s.nbwd.preop_uses_poly(pre))))
-    check_hip(hipStreamWaitEvent(st, last_chain_done_, 0), "chain order");
+  // A DM-trial submission is ordered as a whole: it waits when ANY of its
+  // trials takes the polynomial path, and the next chain waits for its last
+  // trial.  Whether that is the best rule for trial chains (many backward
+  // halves per forward half) has not been measured.
+  if (last_chain_done_ && last_chain_done_ != s.done &&
+      (serial_chains_ > 0 || (serial_chains_ < 0 && uses_poly)))
+    check_hip(hipStreamWaitEvent(s.stream, last_chain_done_, 0),
+              "chain order");
+}
+
+// Forward half, steps 1-3: raw bytes (or samples) -> s.spec, the [Nc]
+// forward spectrum, and the s.mean_power scalar.  Nothing here depends on
+// the DM.
+void PipelineEngine::enqueue_front(Slot& s, const uint8_t* dev_raw,
+                                   const float* dev_samples) {
+  hipStream_t st = s.stream;
+  const bool fr2c = fuse_r2c_;  // r2c pair-combine fused into bwd load
   const float* fft_in = s.samples;
   // fused unpack: for the 2-bit rectangular-window native-forward case the
   // FFT's first column pass decodes the raw bytes itself (0.25 GB of byte
@@ -329,11 +419,56 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
       check_hip(mean_power(s.spec, nc_, s.partials, s.mean_power, st),
                 "meanp");
   }
+}
+
+// Backward half, steps 4-11, at one DM: s.spec -> waterfall -> time series ->
+// detection counters in `row`.  ts_dst (optional) receives a copy of the
+// baseline-subtracted series; the series itself is always produced in s.ts,
+// whose alignment the float4 reductions rely on (a row of the DM-time plane
+// starts at k * ts_count floats, which need not be 16-byte aligned).
+// keep_spectrum = false is the single-DM chain: s.spec is consumed in place.
+// keep_spectrum = true leaves s.spec bit-for-bit intact and works in
+// s.trial_w instead:
+//   fused native backward   first column pass s.spec -> trial_w (the pre-op
+//                           reads, never writes, its input), later passes in
+//                           place in trial_w, final pass -> s.samples
+//   everything else         out-of-place RFI+dedispersion s.spec -> trial_w,
+//                           then the backward transform on trial_w (native:
+//                           -> s.samples; rocFFT/hipFFT: in place, the
+//                           waterfall is trial_w)
+void PipelineEngine::enqueue_back(Slot& s, double dm, const ResultRow& row,
+                                  float* ts_dst, bool keep_spectrum) {
+  hipStream_t st = s.stream;
+  const float2* table = phase_table_;
+  const bool fr2c = fuse_r2c_;
+  // RFI s1 + manual zap + dedispersion fuse into the backward FFT's first
+  // column pass when the native planner allows it (step 4.+5. below)
+  const bool fuse_into_bwd = native_bwd_ && s.nbwd.first_pass_fusable();
+  const FftPreop pre = make_preop(s, dm);
   // 4.+5. RFI s1 + manual zap + dedispersion fused into the backward FFT's
   // first column pass when the native planner allows it (saves a full
   // read+write of the 4 GB spectrum); otherwise the standalone fused kernel.
   float2* wf;
-  if (fuse_into_bwd) {
+  if (keep_spectrum && fuse_into_bwd) {
+    s.nbwd.exec(s.spec, reinterpret_cast<float2*>(s.samples), st, &pre,
+                watfft_window_ ? nullptr : s.sk_dif_partials, nullptr, 2,
+                /*first_pass_out=*/s.trial_w);
+    wf = reinterpret_cast<float2*>(s.samples);
+  } else if (keep_spectrum) {
+    check_hip(rfi_dedisperse_fused(
+                  s.spec, s.trial_w, nc_,
+                  cfg_.enable_rfi_s1 ? s.mean_power : nullptr,
+                  cfg_.rfi_threshold, norm_coeff_, cfg_.zap_ranges,
+                  cfg_.n_zap_ranges, f_min_, f_c_, df_, dm, table, st),
+              "rfi+dedisp oop");
+    if (native_bwd_) {
+      s.nbwd.exec(s.trial_w, reinterpret_cast<float2*>(s.samples), st);
+      wf = reinterpret_cast<float2*>(s.samples);
+    } else {
+      s.plans.exec_c2c_backward(s.trial_w);
+      wf = s.trial_w;
+    }
+  } else if (fuse_into_bwd) {
     s.nbwd.exec(s.spec, reinterpret_cast<float2*>(s.samples), st, &pre,
                 watfft_window_ ? nullptr : s.sk_dif_partials, nullptr, 2,
                 fr2c ? s.xbuf : nullptr);
@@ -358,7 +493,7 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
               "watfft deapply");
 
   const int ncnt = 2 + n_boxcars_;
-  check_hip(hipMemsetAsync(s.counters, 0, ncnt * sizeof(unsigned), st),
+  check_hip(hipMemsetAsync(row.counters, 0, ncnt * sizeof(unsigned), st),
             "memset counters");
 
   const uint8_t* ts_flags = nullptr;
@@ -372,7 +507,7 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
     else
       check_hip(sk_row_stats(wf, s_, l_, s.s2s4, st), "sk stats");
     check_hip(sk_flags(wf, s.s2s4, s_, l_, sk_lo_, sk_hi_, s.flags,
-                       s.counters + 0, st),
+                       row.counters + 0, st),
               "sk flags");
     // NOTE: the waterfall itself is NOT zapped here — the time-series pass
     // below applies the flags directly, and zeroing the flagged rows of the
@@ -391,7 +526,7 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
   // 9. raw-series detection
   check_hip(sum_sumsq(s.ts, ts_count_, s.partials, s.sums, st), "ts var");
   check_hip(count_above(s.ts, ts_count_, s.sums + 1, cfg_.snr_threshold,
-                        s.counters + 1, s.thresholds + 0, st),
+                        row.counters + 1, row.thresholds + 0, st),
             "count raw");
   // 10. boxcar ladder from the inclusive scan — fused: thresholds and
   // counts for every length derive directly from the ~1 MB cumulative sum
@@ -401,23 +536,193 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
               "scan");
     check_hip(boxcar_ladder(s.cumsum, ts_count_, boxcar_lengths_.data(),
                             n_boxcars_, s.box_partials, cfg_.snr_threshold,
-                            s.thresholds + 1, s.counters + 2, st),
+                            row.thresholds + 1, row.counters + 2, st),
               "box ladder");
   }
   // 11. result counters → pinned host
-  check_hip(hipMemcpyAsync(s.h_counters, s.counters, ncnt * sizeof(unsigned),
+  check_hip(hipMemcpyAsync(row.h_counters, row.counters, ncnt * sizeof(unsigned),
                            hipMemcpyDeviceToHost, st),
             "res d2h");
-  check_hip(hipMemcpyAsync(s.h_thresholds, s.thresholds,
+  check_hip(hipMemcpyAsync(row.h_thresholds, row.thresholds,
                            (1 + n_boxcars_) * sizeof(float),
                            hipMemcpyDeviceToHost, st),
             "thr d2h");
-  if (record_event) {
-    check_hip(hipEventRecord(s.done, st), "event record");
-    s.busy = true;
-    last_chain_done_ = s.done;
-  }
+  if (ts_dst)
+    check_hip(hipMemcpyAsync(ts_dst, s.ts, ts_count_ * sizeof(float),
+                             hipMemcpyDeviceToDevice, st),
+              "ts plane row");
+  s.last_row = row;
 }
+
+void PipelineEngine::check_trials(int n_trials) const {
+  if (cfg_.max_dm_trials == 0)
+    throw std::runtime_error(
+        "submit_trials: the engine was built with max_dm_trials = 0");
+  if (cfg_.use_phase_table)
+    throw std::runtime_error(
+        "submit_trials: DM trials need use_phase_table = false (the table "
+        "holds one DM)");
+  if (fuse_r2c_)
+    throw std::runtime_error(
+        "submit_trials: not supported with SRTB_FUSE_R2C=1 (the packed "
+        "spectrum is not the retained r2c spectrum)");
+  if (n_trials < 1 || n_trials > cfg_.max_dm_trials)
+    throw std::runtime_error("submit_trials: n_trials = " +
+                             std::to_string(n_trials) + " outside [1, " +
+                             std::to_string(cfg_.max_dm_trials) + "]");
+}
+
+// One trial: backward half at trial k's DM from the retained spectrum into
+// result row k and plane row k, then the peaks of its detection series.
+void PipelineEngine::enqueue_trial(Slot& s, int k) {
+  hipStream_t st = s.stream;
+  const size_t nthr = 1 + (size_t)n_boxcars_;
+  enqueue_back(s, s.trial_dms[k], trial_row(s, k),
+               s.trial_plane + (size_t)k * ts_count_, /*keep_spectrum=*/true);
+  check_hip(detect_peaks(s.ts, n_boxcars_ > 0 ? s.cumsum : nullptr, ts_count_,
+                         boxcar_lengths_.data(), n_boxcars_, s.peak_scratch,
+                         s.trial_peak_val + k * nthr,
+                         s.trial_peak_idx + k * nthr, st),
+            "detect peaks");
+  check_hip(hipMemcpyAsync(s.h_trial_peak_val + k * nthr,
+                           s.trial_peak_val + k * nthr, nthr * sizeof(float),
+                           hipMemcpyDeviceToHost, st),
+            "peak d2h");
+  check_hip(hipMemcpyAsync(s.h_trial_peak_idx + k * nthr,
+                           s.trial_peak_idx + k * nthr,
+                           nthr * sizeof(unsigned), hipMemcpyDeviceToHost, st),
+            "peak idx d2h");
+  s.cur_trial = k;
+}
+
+void PipelineEngine::enqueue_trials(Slot& s, const uint8_t* dev_raw,
+                                    const float* dev_samples,
+                                    const double* dms, int n_trials) {
+  RoctxRange r_chain("srtb_block_trials");
+  s.trial_dms.assign(dms, dms + n_trials);
+  bool any_poly = false;
+  if (serial_chains_ < 0 && native_bwd_ && s.nbwd.first_pass_fusable())
+    for (int k = 0; k < n_trials && !any_poly; ++k)
+      any_poly = s.nbwd.preop_uses_poly(make_preop(s, dms[k]));
+  order_after_last_chain(s, any_poly);
+  enqueue_front(s, dev_raw, dev_samples);
+  for (int k = 0; k < n_trials; ++k) enqueue_trial(s, k);
+  check_hip(hipEventRecord(s.done, s.stream), "event record");
+  s.busy = true;
+  last_chain_done_ = s.done;
+}
+
+PipelineEngine::Slot& PipelineEngine::acquire_slot(int& id) {
+  id = next_slot_;
+  next_slot_ = (next_slot_ + 1) % n_slots_;
+  Slot& s = *slots_[id];
+  if (s.busy) {
+    check_hip(hipEventSynchronize(s.done), "slot wait");
+    s.busy = false;
+  }
+  return s;
+}
+
+int PipelineEngine::submit_trials(const void* host_bytes, size_t nbytes,
+                                  const double* dms, int n_trials) {
+  if (nbytes != raw_bytes_)
+    throw std::runtime_error("submit_trials: wrong size");
+  check_trials(n_trials);
+  int id;
+  Slot& s = acquire_slot(id);
+  check_hip(hipMemcpyAsync(s.raw, host_bytes, nbytes, hipMemcpyHostToDevice,
+                           s.stream),
+            "raw h2d");
+  enqueue_trials(s, s.raw, nullptr, dms, n_trials);
+  return id;
+}
+
+int PipelineEngine::submit_trials_device(const void* dev_bytes, size_t nbytes,
+                                         const double* dms, int n_trials,
+                                         hipEvent_t wait_event) {
+  if (nbytes != raw_bytes_)
+    throw std::runtime_error("submit_trials: wrong size");
+  check_trials(n_trials);
+  int id;
+  Slot& s = acquire_slot(id);
+  if (wait_event)
+    check_hip(hipStreamWaitEvent(s.stream, wait_event, 0), "producer wait");
+  enqueue_trials(s, static_cast<const uint8_t*>(dev_bytes), nullptr, dms,
+                 n_trials);
+  return id;
+}
+
+int PipelineEngine::submit_trials_samples_device(const float* dev_samples,
+                                                 size_t count,
+                                                 const double* dms,
+                                                 int n_trials,
+                                                 hipEvent_t wait_event) {
+  if (count != n_)
+    throw std::runtime_error("submit_trials_samples: wrong count");
+  check_trials(n_trials);
+  int id;
+  Slot& s = acquire_slot(id);
+  if (wait_event)
+    check_hip(hipStreamWaitEvent(s.stream, wait_event, 0), "fanout wait");
+  enqueue_trials(s, nullptr, dev_samples, dms, n_trials);
+  return id;
+}
+
+std::vector<TrialResult> PipelineEngine::wait_trials(int slot) {
+  Slot& s = *slots_.at(slot);
+  if (s.trial_dms.empty())
+    throw std::runtime_error(
+        "wait_trials: the slot's last submission carried no trials");
+  check_hip(hipEventSynchronize(s.done), "wait trials");
+  s.busy = false;
+  s.wf_zap_pending = cfg_.enable_sk;  // see waterfall_ptr()
+  const size_t ncnt = 2 + (size_t)n_boxcars_, nthr = 1 + (size_t)n_boxcars_;
+  std::vector<TrialResult> out(s.trial_dms.size());
+  for (size_t k = 0; k < out.size(); ++k) {
+    TrialResult& t = out[k];
+    const unsigned* c = s.h_trial_counters + k * ncnt;
+    const float* thr = s.h_trial_thresholds + k * nthr;
+    t.dm = s.trial_dms[k];
+    t.result.zero_count = c[0];
+    t.result.counts.emplace_back(1u, c[1]);
+    for (int b = 0; b < n_boxcars_; ++b)
+      t.result.counts.emplace_back((unsigned)boxcar_lengths_[b], c[2 + b]);
+    t.result.thresholds.assign(thr, thr + nthr);
+    for (size_t j = 0; j < nthr; ++j) {
+      TrialPeak p;
+      p.boxcar_length = j == 0 ? 1u : (unsigned)boxcar_lengths_[j - 1];
+      p.value = s.h_trial_peak_val[k * nthr + j];
+      p.index = s.h_trial_peak_idx[k * nthr + j];
+      p.snr = p.value / (thr[j] / cfg_.snr_threshold);
+      t.peaks.push_back(p);
+    }
+  }
+  return out;
+}
+
+void PipelineEngine::select_trial(int slot, int k) {
+  Slot& s = *slots_.at(slot);
+  if (k < 0 || (size_t)k >= s.trial_dms.size())
+    throw std::runtime_error(
+        "select_trial: no such trial in the slot's last submission");
+  if (k == s.cur_trial) return;
+  enqueue_trial(s, k);
+  check_hip(hipEventRecord(s.done, s.stream), "event record");
+  s.busy = true;
+  s.wf_zap_pending = cfg_.enable_sk;  // the new waterfall is not zapped yet
+}
+
+float* PipelineEngine::dm_time_plane_ptr(int slot) {
+  Slot& s = *slots_.at(slot);
+  if (!s.trial_plane)
+    throw std::runtime_error("dm_time_plane: max_dm_trials = 0");
+  return s.trial_plane;
+}
+
+int PipelineEngine::n_trials(int slot) const {
+  return (int)slots_.at(slot)->trial_dms.size();
+}
+
 
 int PipelineEngine::submit(const void* host_bytes, size_t nbytes,
                            double dm_override) {
@@ -435,6 +740,9 @@ int PipelineEngine::submit(const void* host_bytes, size_t nbytes,
     check_hip(hipGraphLaunch(s.graph_exec, s.stream), "graph launch");
     check_hip(hipEventRecord(s.done, s.stream), "event record");
     s.busy = true;
+    s.last_row = plain_row(s);  // a trial submission may have come between
+    s.trial_dms.clear();
+    s.cur_trial = -1;
     return id;
   }
   if (graph_ok && s.graph_pending >= 1 && !s.graph_exec) {
@@ -507,11 +815,14 @@ BlockResult PipelineEngine::wait(int slot) {
   s.busy = false;
   s.wf_zap_pending = cfg_.enable_sk;  // see waterfall_ptr()
   BlockResult r;
-  r.zero_count = s.h_counters[0];
-  r.counts.emplace_back(1u, s.h_counters[1]);
+  // the plain row, or after a trial submission the row of the last trial run
+  const unsigned* hc = s.last_row.h_counters;
+  const float* ht = s.last_row.h_thresholds;
+  r.zero_count = hc[0];
+  r.counts.emplace_back(1u, hc[1]);
   for (int b = 0; b < n_boxcars_; ++b)
-    r.counts.emplace_back((unsigned)boxcar_lengths_[b], s.h_counters[2 + b]);
-  r.thresholds.assign(s.h_thresholds, s.h_thresholds + 1 + n_boxcars_);
+    r.counts.emplace_back((unsigned)boxcar_lengths_[b], hc[2 + b]);
+  r.thresholds.assign(ht, ht + 1 + n_boxcars_);
   return r;
 }
 

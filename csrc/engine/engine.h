@@ -60,13 +60,37 @@ struct EngineConfig {
   // per slot and replay it; falls back to direct enqueue whenever the
   // submission differs from the captured one (dm override, other host ptr)
   bool use_hip_graph = false;
+  // DM-trial search (submit_trials): the largest number of trials one
+  // submission may carry.  0 = the mode is off and nothing is allocated;
+  // T > 0 adds per slot one [Nc] work buffer, a [T][ts_count] DM-time plane
+  // and T result rows.  At most kMaxDmTrials.
+  int max_dm_trials = 0;
 };
+
+constexpr int kMaxDmTrials = 256;
 
 struct BlockResult {
   unsigned zero_count = 0;  // zapped-channel count (gate detections on host)
   // (boxcar_length, signal_count) — boxcar_length 1 is the raw series
   std::vector<std::pair<unsigned, unsigned>> counts;
   std::vector<float> thresholds;
+};
+
+// Peak of one detection series of one trial: the maximum, the lowest sample
+// index attaining it (boxcar's indexing: the window starts after `index`) and
+// the maximum in units of the rms the detection threshold is built from,
+// snr = value / (threshold / snr_threshold).
+struct TrialPeak {
+  unsigned boxcar_length = 1;  // 1 = the raw series
+  float value = 0;
+  unsigned index = 0;
+  float snr = 0;
+};
+
+struct TrialResult {
+  double dm = 0;
+  BlockResult result;
+  std::vector<TrialPeak> peaks;  // raw series, then one per ladder length
 };
 
 class PipelineEngine {
@@ -101,8 +125,39 @@ class PipelineEngine {
                             double dm_override = NAN,
                             hipEvent_t wait_event = nullptr);
 
-  // Wait for a slot's chain and return its detection counters.
+  // DM-trial search: ONE forward half (unpack, forward FFT, r2c finish,
+  // mean power) per block, then one backward half per trial DM, each from
+  // the block's forward spectrum, which stays intact in the slot.  Trial k
+  // fills result row k and row k of the DM-time plane and is followed by the
+  // peak search.  Everything runs on the slot's stream with one `done` event
+  // at the end; never through the hipGraph path.  Needs max_dm_trials > 0
+  // and use_phase_table = false; 1 <= n_trials <= max_dm_trials.
+  int submit_trials(const void* host_bytes, size_t nbytes, const double* dms,
+                    int n_trials);
+  int submit_trials_device(const void* dev_bytes, size_t nbytes,
+                           const double* dms, int n_trials,
+                           hipEvent_t wait_event = nullptr);
+  int submit_trials_samples_device(const float* dev_samples, size_t count,
+                                   const double* dms, int n_trials,
+                                   hipEvent_t wait_event = nullptr);
+
+  // Wait for a slot's chain and return its detection counters.  After a
+  // trial submission: those of the trial most recently run.
   BlockResult wait(int slot);
+
+  // Wait for a slot's trial submission and return every trial's result.
+  std::vector<TrialResult> wait_trials(int slot);
+
+  // Re-run trial k's backward half from the retained spectrum on the slot's
+  // stream (asynchronous; rewrites result row k and plane row k with the same
+  // values) so that waterfall_ptr, time_series_ptr, cumsum_ptr and
+  // compute_boxcar* refer to trial k.  No-op when k was the last trial run.
+  // Valid until the slot is submitted again.
+  void select_trial(int slot, int k);
+
+  // [n_trials(slot)][ts_count] baseline-subtracted series, one row per trial.
+  float* dm_time_plane_ptr(int slot);
+  int n_trials(int slot) const;  // trials of the slot's last submission
 
   // Wait for all outstanding work.
   void synchronize();
@@ -134,9 +189,31 @@ class PipelineEngine {
 
  private:
   struct Slot;
+  // where one backward half leaves its counters and thresholds
+  struct ResultRow {
+    unsigned* counters = nullptr;    // device [2 + n_boxcars]
+    float* thresholds = nullptr;     // device [1 + n_boxcars]
+    unsigned* h_counters = nullptr;  // pinned mirrors
+    float* h_thresholds = nullptr;
+  };
   void enqueue_chain(Slot& s, const uint8_t* dev_raw,
                      const float* dev_samples, double dm,
                      bool record_event = true);
+  // the chain's two halves, see engine.cpp
+  void enqueue_front(Slot& s, const uint8_t* dev_raw,
+                     const float* dev_samples);
+  void enqueue_back(Slot& s, double dm, const ResultRow& row, float* ts_dst,
+                    bool keep_spectrum);
+  FftPreop make_preop(const Slot& s, double dm) const;
+  void order_after_last_chain(Slot& s, bool uses_poly);
+  ResultRow plain_row(Slot& s) const;
+  ResultRow trial_row(Slot& s, int k) const;
+  Slot& acquire_slot(int& id);
+  void enqueue_trials(Slot& s, const uint8_t* dev_raw,
+                      const float* dev_samples, const double* dms,
+                      int n_trials);
+  void enqueue_trial(Slot& s, int k);
+  void check_trials(int n_trials) const;
 
   EngineConfig cfg_;
   size_t n_, nc_, s_, l_, ts_count_, raw_bytes_;
@@ -190,6 +267,21 @@ class PipelineEngine {
     hipGraphExec_t graph_exec = nullptr;
     const void* graph_host_src = nullptr;  // host ptr the capture used
     int graph_pending = 0;  // submissions seen for this slot
+    // DM-trial state (allocated only with max_dm_trials > 0)
+    float2* trial_w = nullptr;        // [Nc] per-trial backward working set
+    float* trial_plane = nullptr;     // [T][ts_count]
+    unsigned* trial_counters = nullptr;   // [T][2 + n_boxcars]
+    float* trial_thresholds = nullptr;    // [T][1 + n_boxcars]
+    float* trial_peak_val = nullptr;      // [T][1 + n_boxcars]
+    unsigned* trial_peak_idx = nullptr;   // [T][1 + n_boxcars]
+    unsigned* h_trial_counters = nullptr;  // pinned mirrors of the four
+    float* h_trial_thresholds = nullptr;
+    float* h_trial_peak_val = nullptr;
+    unsigned* h_trial_peak_idx = nullptr;
+    void* peak_scratch = nullptr;
+    std::vector<double> trial_dms;  // of the last trial submission
+    int cur_trial = -1;             // trial whose products the slot holds
+    ResultRow last_row;             // row of the back half most recently run
   };
   std::vector<std::unique_ptr<Slot>> slots_;
   int next_slot_ = 0;

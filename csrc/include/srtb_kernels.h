@@ -92,6 +92,17 @@ hipError_t rfi_dedisperse_fused(float2* spec, size_t n,
                                 double df, double dm,
                                 const float2* factor_table,
                                 hipStream_t stream);
+// Out-of-place form: reads `in`, writes every bin of `out`; `in` is never
+// written (the DM-trial path keeps it as the block's forward spectrum).
+// out == in is the in-place kernel above; otherwise the two buffers must not
+// overlap.
+hipError_t rfi_dedisperse_fused(const float2* in, float2* out, size_t n,
+                                const double* mean_power, float threshold,
+                                float norm_coeff, const ZapRange* ranges,
+                                int n_ranges, double f_min, double f_c,
+                                double df, double dm,
+                                const float2* factor_table,
+                                hipStream_t stream);
 
 // ---------------- spectral kurtosis (stage 2) ----------------
 // Per-row <sum |x|^2, sum |x|^4> of a [rows][len] waterfall; one workgroup
@@ -177,6 +188,20 @@ hipError_t boxcar_ladder(const float* cumsum, size_t ts_count,
 
 hipError_t boxcar(const float* cumsum, float* out, size_t n_out, size_t L,
                   hipStream_t stream);
+
+// Peaks of the raw series and of every ladder length in one pass:
+//   out_value[0], out_index[0]     = max ts[i] and the lowest i attaining it
+//   out_value[1+l], out_index[1+l] = the same over cumsum[i+L_l] - cumsum[i],
+//                                    i + L_l < ts_count (boxcar's indexing)
+// Deterministic and independent of the launch geometry.  A length with no
+// valid window reports -infinity at index UINT_MAX.  scratch: device memory
+// of detect_peaks_scratch_bytes(), no initialization needed.  cumsum may be
+// null when n_lengths == 0; n_lengths <= 12, ts_count < 2^32.
+size_t detect_peaks_scratch_bytes();
+hipError_t detect_peaks(const float* ts, const float* cumsum, size_t ts_count,
+                        const size_t* lengths, int n_lengths, void* scratch,
+                        float* out_value, unsigned* out_index,
+                        hipStream_t stream);
 
 // ---------------- hand-written Stockham FFT ----------------
 // One generic pass of the LDS-staged Stockham FFT (csrc/kernels/fft.hip).

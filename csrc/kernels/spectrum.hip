@@ -114,13 +114,26 @@ __device__ inline float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
+// cmul with the contraction written out (one rounded product, one fma per
+// component, as the compiler has always contracted it in the in-place
+// kernel): the fused kernel's result must not depend on how a given
+// instantiation happens to be contracted.
+__device__ inline float2 cmul_fma(float2 a, float2 b) {
+  return make_float2(__builtin_fmaf(a.x, b.x, -(a.y * b.y)),
+                     __builtin_fmaf(a.x, b.y, a.y * b.x));
+}
+
 struct ZapRangesArg {
   ZapRange r[16];
   int count;
 };
 
+// `in` and `out` are either the same buffer (the single-DM chain, in place)
+// or disjoint (DM trials: `in` is the retained forward spectrum and is never
+// written).  One kernel serves both so that both run the same arithmetic;
+// neither pointer is __restrict__ because they may alias exactly.
 template <bool kTable, bool kRfi>
-__global__ void k_rfi_dedisp_fused(float2* __restrict__ spec, size_t n,
+__global__ void k_rfi_dedisp_fused(const float2* in, float2* out, size_t n,
                                    const double* __restrict__ mean_power,
                                    float threshold, float norm_coeff,
                                    ZapRangesArg zaps, double f_min, double f_c,
@@ -130,7 +143,7 @@ __global__ void k_rfi_dedisp_fused(float2* __restrict__ spec, size_t n,
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
-    float2 v = spec[i];
+    float2 v = in[i];
     bool zap = false;
     if constexpr (kRfi) {
       zap = norm2(v) > thr_mean;
@@ -138,7 +151,7 @@ __global__ void k_rfi_dedisp_fused(float2* __restrict__ spec, size_t n,
     for (int z = 0; z < zaps.count; ++z)
       zap |= (i >= zaps.r[z].lo) & (i <= zaps.r[z].hi);
     if (zap) {
-      spec[i] = make_float2(0.0f, 0.0f);
+      out[i] = make_float2(0.0f, 0.0f);
     } else {
       if constexpr (kRfi) {
         v.x *= norm_coeff;
@@ -146,7 +159,7 @@ __global__ void k_rfi_dedisp_fused(float2* __restrict__ spec, size_t n,
       }
       const float2 fac =
           kTable ? table[i] : dedisp_factor(i, f_min, f_c, df, dm);
-      spec[i] = cmul(v, fac);
+      out[i] = cmul_fma(v, fac);
     }
   }
 }
@@ -585,6 +598,108 @@ __global__ void k_box_count(const float* __restrict__ cumsum, size_t ts_count,
   }
 }
 
+// ---- per-trial peaks: maximum + lowest index attaining it ----
+// Raw series and every ladder length in ONE pass over ts / the (L2-resident)
+// cumulative sum, as k_box_stats.  Each candidate is packed into a 64-bit
+// ordered key: high word = the float's bits mapped to an order-preserving
+// unsigned, low word = ~index, so an unsigned max picks the largest value
+// and, among equals, the lowest index.  max is associative and commutative,
+// so the two-stage reduce (per-workgroup keys -> one finishing workgroup) is
+// exact and independent of the launch geometry; it needs no atomics and no
+// zeroed scratch, unlike a 64-bit atomicMax on a per-trial cell.
+
+constexpr int kPeakBlocks = 256;
+constexpr int kPeakSlots = 13;  // raw + 12 ladder lengths
+
+__device__ __forceinline__ unsigned long long peak_key(float v, size_t i) {
+  if (v == 0.0f) v = 0.0f;  // -0 and +0 compare equal: give them one key
+  const unsigned b = __float_as_uint(v);
+  const unsigned o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return ((unsigned long long)o << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)i);
+}
+
+__device__ __forceinline__ unsigned long long peak_key_init() {
+  // -infinity, "no index": an all-negative series keeps its negative maximum
+  return (unsigned long long)(~0xFF800000u) << 32;
+}
+
+__device__ __forceinline__ unsigned long long peak_max(unsigned long long a,
+                                                       unsigned long long b) {
+  return a > b ? a : b;
+}
+
+// Block-level max over kBlock threads; valid on thread 0.
+__device__ inline unsigned long long block_reduce_peak(unsigned long long k) {
+  __shared__ unsigned long long lds[kBlock / 64];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    k = peak_max(k, __shfl_down(k, off, 64));
+  if (lane == 0) lds[wave] = k;
+  __syncthreads();
+  unsigned long long out = peak_key_init();
+  if (wave == 0) {
+    out = (lane < kBlock / 64) ? lds[lane] : peak_key_init();
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+      out = peak_max(out, __shfl_down(out, off, 64));
+  }
+  __syncthreads();
+  return out;
+}
+
+__global__ void k_peaks_partial(const float* __restrict__ ts,
+                                const float* __restrict__ cumsum,
+                                size_t ts_count, BoxLadderDev lad,
+                                unsigned long long* __restrict__ partial) {
+  unsigned long long key[kPeakSlots];
+#pragma unroll
+  for (int l = 0; l < kPeakSlots; ++l) key[l] = peak_key_init();
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+       i < ts_count; i += stride) {
+    key[0] = peak_max(key[0], peak_key(ts[i], i));
+    if (lad.n > 0) {
+      const float c0 = cumsum[i];
+#pragma unroll
+      for (int l = 0; l < 12; ++l) {
+        if (l < lad.n) {
+          const unsigned long long L = lad.L[l];
+          if (i + L < ts_count)
+            key[1 + l] = peak_max(key[1 + l], peak_key(cumsum[i + L] - c0, i));
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < kPeakSlots; ++l) {
+    if (l <= lad.n) {
+      const unsigned long long b = block_reduce_peak(key[l]);
+      if (threadIdx.x == 0)
+        partial[(size_t)l * kPeakBlocks + blockIdx.x] = b;
+    }
+  }
+}
+
+__global__ void k_peaks_finish(const unsigned long long* __restrict__ partial,
+                               int n_blocks, int n_slots,
+                               float* __restrict__ out_value,
+                               unsigned* __restrict__ out_index) {
+  for (int l = 0; l < n_slots; ++l) {
+    unsigned long long k = peak_key_init();
+    for (int i = threadIdx.x; i < n_blocks; i += blockDim.x)
+      k = peak_max(k, partial[(size_t)l * kPeakBlocks + i]);
+    k = block_reduce_peak(k);
+    if (threadIdx.x == 0) {
+      const unsigned o = (unsigned)(k >> 32);
+      const unsigned b = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
+      out_value[l] = __uint_as_float(b);
+      out_index[l] = 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull);
+    }
+  }
+}
+
 }  // namespace
 
 // ---------------- host wrappers ----------------
@@ -645,13 +760,20 @@ hipError_t dedisp_phase_table(float2* table, size_t n, double f_min,
   return hipSuccess;
 }
 
-hipError_t rfi_dedisperse_fused(float2* spec, size_t n, const double* mean_p,
-                                float threshold, float norm_coeff,
-                                const ZapRange* ranges, int n_ranges,
-                                double f_min, double f_c, double df, double dm,
+hipError_t rfi_dedisperse_fused(const float2* in, float2* out, size_t n,
+                                const double* mean_p, float threshold,
+                                float norm_coeff, const ZapRange* ranges,
+                                int n_ranges, double f_min, double f_c,
+                                double df, double dm,
                                 const float2* factor_table,
                                 hipStream_t stream) {
   if (n_ranges > 16) return hipErrorInvalidValue;
+  if (out != in) {
+    // exactly aliased or disjoint: a partial overlap would race
+    const float2* lo = in < out ? in : out;
+    const float2* hi = in < out ? out : in;
+    if (lo + n > hi) return hipErrorInvalidValue;
+  }
   ZapRangesArg za{};
   za.count = n_ranges;
   for (int i = 0; i < n_ranges; ++i) za.r[i] = ranges[i];
@@ -660,24 +782,35 @@ hipError_t rfi_dedisperse_fused(float2* spec, size_t n, const double* mean_p,
   if (factor_table) {
     if (rfi)
       hipLaunchKernelGGL((k_rfi_dedisp_fused<true, true>), g, dim3(kBlock), 0,
-                         stream, spec, n, mean_p, threshold, norm_coeff, za,
+                         stream, in, out, n, mean_p, threshold, norm_coeff, za,
                          f_min, f_c, df, dm, factor_table);
     else
       hipLaunchKernelGGL((k_rfi_dedisp_fused<true, false>), g, dim3(kBlock), 0,
-                         stream, spec, n, mean_p, threshold, norm_coeff, za,
+                         stream, in, out, n, mean_p, threshold, norm_coeff, za,
                          f_min, f_c, df, dm, factor_table);
   } else {
     if (rfi)
       hipLaunchKernelGGL((k_rfi_dedisp_fused<false, true>), g, dim3(kBlock), 0,
-                         stream, spec, n, mean_p, threshold, norm_coeff, za,
+                         stream, in, out, n, mean_p, threshold, norm_coeff, za,
                          f_min, f_c, df, dm, factor_table);
     else
       hipLaunchKernelGGL((k_rfi_dedisp_fused<false, false>), g, dim3(kBlock),
-                         0, stream, spec, n, mean_p, threshold, norm_coeff, za,
-                         f_min, f_c, df, dm, factor_table);
+                         0, stream, in, out, n, mean_p, threshold, norm_coeff,
+                         za, f_min, f_c, df, dm, factor_table);
   }
   SRTB_CHECK_LAUNCH();
   return hipSuccess;
+}
+
+hipError_t rfi_dedisperse_fused(float2* spec, size_t n, const double* mean_p,
+                                float threshold, float norm_coeff,
+                                const ZapRange* ranges, int n_ranges,
+                                double f_min, double f_c, double df, double dm,
+                                const float2* factor_table,
+                                hipStream_t stream) {
+  return rfi_dedisperse_fused(spec, spec, n, mean_p, threshold, norm_coeff,
+                              ranges, n_ranges, f_min, f_c, df, dm,
+                              factor_table, stream);
 }
 
 hipError_t sk_row_stats(const float2* wf, size_t rows, size_t len,
@@ -857,6 +990,31 @@ hipError_t boxcar_ladder(const float* cumsum, size_t ts_count,
                      partials, ts_count, lad, snr, out_thr);
   hipLaunchKernelGGL(k_box_count, grid_for(ts_count), dim3(kBlock), 0,
                      stream, cumsum, ts_count, lad, out_thr, out_counts);
+  SRTB_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+size_t detect_peaks_scratch_bytes() {
+  return (size_t)kPeakSlots * kPeakBlocks * sizeof(unsigned long long);
+}
+
+hipError_t detect_peaks(const float* ts, const float* cumsum, size_t ts_count,
+                        const size_t* lengths, int n_lengths, void* scratch,
+                        float* out_value, unsigned* out_index,
+                        hipStream_t stream) {
+  // indices travel in the low word of the 64-bit key
+  if (n_lengths < 0 || n_lengths > 12 || ts_count == 0 ||
+      ts_count > 0xFFFFFFFFull || (n_lengths > 0 && !cumsum))
+    return hipErrorInvalidValue;
+  BoxLadderDev lad{};
+  lad.n = n_lengths;
+  for (int l = 0; l < n_lengths; ++l) lad.L[l] = lengths[l];
+  const dim3 g = grid_for(ts_count, kBlock, kPeakBlocks);
+  auto* partial = static_cast<unsigned long long*>(scratch);
+  hipLaunchKernelGGL(k_peaks_partial, g, dim3(kBlock), 0, stream, ts, cumsum,
+                     ts_count, lad, partial);
+  hipLaunchKernelGGL(k_peaks_finish, dim3(1), dim3(kBlock), 0, stream, partial,
+                     (int)g.x, 1 + n_lengths, out_value, out_index);
   SRTB_CHECK_LAUNCH();
   return hipSuccess;
 }

@@ -20,7 +20,9 @@ from .utils.expr import evaluate, evaluate_int
 
 # key -> type tag used when assigning parsed strings.
 # "int" / "real" go through the expression evaluator; "str" is verbatim;
-# "bool" accepts 0/1 expressions; "strlist"/"intlist" are comma-separated.
+# "bool" accepts 0/1 expressions; "strlist"/"intlist" are comma-separated;
+# "reallist" is a comma-separated list of expressions kept as its string
+# (checked on assignment, evaluated by the matching helper).
 _FIELD_KINDS = {
     "config_file_name": "str",
     "baseband_input_count": "int",
@@ -31,6 +33,7 @@ _FIELD_KINDS = {
     "baseband_sample_rate": "real",
     "baseband_reserve_sample": "bool",
     "dm": "real",
+    "dm_trial_list": "reallist",
     "udp_receiver_address": "strlist",
     "udp_receiver_port": "intlist",
     "udp_receiver_cpu_preferred": "intlist",
@@ -68,6 +71,8 @@ class Config:
     baseband_sample_rate: float = 1000 * 1e6
     baseband_reserve_sample: bool = True
     dm: float = 0.0
+    # DM-trial search: comma-separated expressions, "" = single-DM operation
+    dm_trial_list: str = ""
     udp_receiver_address: List[str] = field(default_factory=lambda: ["10.0.1.2"])
     udp_receiver_port: List[int] = field(default_factory=lambda: [12004])
     udp_receiver_cpu_preferred: List[int] = field(default_factory=lambda: [0])
@@ -109,6 +114,9 @@ class Config:
             value = [s.strip() for s in raw.split(",") if s.strip()]
         elif kind == "intlist":
             value = [evaluate_int(s) for s in raw.split(",") if s.strip()]
+        elif kind == "reallist":
+            _parse_real_list(raw)  # a malformed list is rejected here
+            value = raw
         else:  # pragma: no cover
             raise AssertionError(kind)
         setattr(self, key, value)
@@ -130,6 +138,10 @@ class Config:
         """Time bins per block in the waterfall (= Nc / spectrum_channel_count)."""
         return max(1, self.nsamps_complex // self.spectrum_channel_count)
 
+    def dm_trials(self) -> List[float]:
+        """The trial DMs of ``dm_trial_list`` ([] when the key is unset)."""
+        return _parse_real_list(self.dm_trial_list)
+
     def copy(self) -> "Config":
         return dataclasses.replace(
             self,
@@ -137,6 +149,14 @@ class Config:
             udp_receiver_port=list(self.udp_receiver_port),
             udp_receiver_cpu_preferred=list(self.udp_receiver_cpu_preferred),
         )
+
+
+def _parse_real_list(raw: str) -> List[float]:
+    """Comma-separated arithmetic expressions -> floats.  Empty items are an
+    error except for an entirely empty list."""
+    if not raw.strip():
+        return []
+    return [float(evaluate(item)) for item in raw.split(",")]
 
 
 def parse_config_file(path: str, cfg: Config | None = None) -> Config:

@@ -4,7 +4,11 @@
   streams (naocpsr_snap1 / gznupsr_a1 / byte-interleaved cpsr2), each run
   through the full chain (reference unpack_pipe.hpp:146-390 fan-out).
 - DmTrialSweep: coherent DM-trial search over one block (Crab giant-pulse
-  search config of BASELINE.json) using the engine's per-submit DM override.
+  search config of BASELINE.json) using the engine's per-submit DM override:
+  one whole chain per trial.
+- DmTrialSearch: the same search from ONE forward spectrum per block (engine
+  submit_trials): only the backward half runs per trial, and the per-trial
+  peak S/N, boxcar width and arrival sample are found on the GPU.
 """
 
 from __future__ import annotations
@@ -18,7 +22,8 @@ from ..config import Config
 
 
 def _make_engine(C, cfg: Config, nsamps_reserved: int, nbits: int,
-                 n: int | None = None, n_slots: int = 2):
+                 n: int | None = None, n_slots: int = 2,
+                 max_dm_trials: int = 0):
     nc = (n or cfg.baseband_input_count) // 2
     ranges = ref.parse_rfi_freq_list(cfg.mitigate_rfi_freq_list)
     bins = ref.rfi_ranges_to_bins(cfg.baseband_freq_low,
@@ -34,7 +39,7 @@ def _make_engine(C, cfg: Config, nsamps_reserved: int, nbits: int,
         nsamps_reserved=nsamps_reserved,
         zap_ranges=[[int(a), int(b)] for a, b in bins],
         use_phase_table=False, enable_rfi_s1=True, enable_sk=True,
-        n_slots=n_slots)
+        n_slots=n_slots, max_dm_trials=max_dm_trials)
 
 
 class DualPolPipeline:
@@ -98,9 +103,11 @@ class DmTrial:
 class DmTrialSweep:
     """Coherent DM-trial sweep over one baseband block.
 
-    The block is uploaded once; each trial re-runs the chain from the R2C
-    spectrum with a different dedispersion DM (on-the-fly fp64 phase).  The
-    best trial is the one with the highest peak SNR in its time series.
+    The block is uploaded once; each trial then re-runs the WHOLE chain
+    (unpack, forward FFT, r2c finish, mean power, and the backward half) with
+    a different dedispersion DM (on-the-fly phase) — nothing is reused between
+    trials.  DmTrialSearch shares the forward half.  The best trial is the one
+    with the highest peak SNR in its time series.
     """
 
     def __init__(self, cfg: Config, nsamps_reserved: int = 0):
@@ -143,3 +150,65 @@ class DmTrialSweep:
 
     def best(self, trials: list[DmTrial]) -> DmTrial:
         return max(trials, key=lambda t: t.peak_snr)
+
+
+@dataclass
+class DmTrialResult:
+    dm: float
+    counts: list
+    zero_count: int
+    peak_snr: float    # highest peak S/N over the raw series and the ladder
+    peak_boxcar: int   # boxcar length attaining it (1 = raw series)
+    peak_index: int    # its sample index (boxcar indexing)
+
+
+class DmTrialSearch:
+    """Coherent DM-trial search from one forward spectrum per block.
+
+    The engine runs the forward half of the chain once per block and keeps
+    the spectrum on the device; every trial DM runs only the backward half
+    (RFI + dedispersion, waterfall transform, detection) from it.  Peaks come
+    from the GPU, in units of the rms the detection threshold uses, so no
+    per-trial host pass over the series is needed.  Both engine slots are
+    used: block i+1 uploads while block i runs its trials.
+    """
+
+    def __init__(self, cfg: Config, dms: list[float],
+                 nsamps_reserved: int = 0):
+        import torch
+        from ..ops import native
+        self.torch = torch
+        self.C = native()
+        self.cfg = cfg
+        self.dms = [float(d) for d in dms]
+        if not self.dms:
+            raise ValueError("DmTrialSearch needs at least one trial DM")
+        self.eng = _make_engine(self.C, cfg, nsamps_reserved,
+                                nbits=cfg.baseband_input_bits,
+                                max_dm_trials=len(self.dms))
+
+    def submit(self, raw) -> dict:
+        """Enqueue one block's trials; raw is a numpy array or a (host or
+        device) tensor of the block's bytes.  The handle keeps the block
+        alive until wait()."""
+        torch = self.torch
+        if not isinstance(raw, torch.Tensor):
+            raw = torch.from_numpy(np.ascontiguousarray(raw))
+        return {"slot": self.eng.submit_trials(raw, self.dms), "raw": raw}
+
+    def wait(self, handle: dict) -> list[DmTrialResult]:
+        out = []
+        for t in self.eng.wait_trials(handle["slot"]):
+            p = max(t["peaks"], key=lambda q: q["snr"])
+            out.append(DmTrialResult(
+                dm=float(t["dm"]), counts=t["counts"],
+                zero_count=t["zero_count"], peak_snr=float(p["snr"]),
+                peak_boxcar=int(p["boxcar_length"]),
+                peak_index=int(p["index"])))
+        return out
+
+    def search(self, raw) -> list[DmTrialResult]:
+        return self.wait(self.submit(raw))
+
+    def best(self, results: list[DmTrialResult]) -> DmTrialResult:
+        return max(results, key=lambda t: t.peak_snr)
