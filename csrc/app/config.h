@@ -204,6 +204,12 @@ struct Config {
   size_t gui_pixmap_width = 1920;
   size_t gui_pixmap_height = 1080;
   int log_level = 3;
+  // continuous SIGPROC filterbank output ("" = off), twin of the Python keys
+  std::string filterbank_output_path;
+  size_t filterbank_tscrunch = 16;
+  size_t filterbank_fscrunch = 1;
+  int filterbank_nbits = 8;
+  double filterbank_tstart_mjd = 0.0;
 
   void assign(const std::string& key, const std::string& raw);
   void parse_file(const std::string& path);
@@ -273,6 +279,11 @@ inline void Config::assign(const std::string& key, const std::string& raw0) {
   else if (key == "gui_pixmap_width") gui_pixmap_width = I();
   else if (key == "gui_pixmap_height") gui_pixmap_height = I();
   else if (key == "log_level") log_level = (int)Expr::eval_int(raw);
+  else if (key == "filterbank_output_path") filterbank_output_path = raw;
+  else if (key == "filterbank_tscrunch") filterbank_tscrunch = I();
+  else if (key == "filterbank_fscrunch") filterbank_fscrunch = I();
+  else if (key == "filterbank_nbits") filterbank_nbits = (int)Expr::eval_int(raw);
+  else if (key == "filterbank_tstart_mjd") filterbank_tstart_mjd = D();
   else throw std::runtime_error("unknown config key: " + key);
 }
 
@@ -346,6 +357,15 @@ inline std::string Config::dump() const {
     for (size_t i = 0; i < dm_trial_list.size(); ++i)
       o << (i ? "," : "") << dm_trial_list[i];
     o << "\n";
+  }
+  if (!filterbank_output_path.empty()) {
+    const auto prec = o.precision(17);
+    o << "filterbank_output_path = " << filterbank_output_path << "\n"
+      << "filterbank_tscrunch = " << filterbank_tscrunch << "\n"
+      << "filterbank_fscrunch = " << filterbank_fscrunch << "\n"
+      << "filterbank_nbits = " << filterbank_nbits << "\n"
+      << "filterbank_tstart_mjd = " << filterbank_tstart_mjd << "\n";
+    o.precision(prec);
   }
   return o.str();
 }

@@ -42,7 +42,8 @@ using srtb_hip::PipelineEngine;
 namespace {
 
 // reference coherent_dedispersion.hpp:87-128 (Python twin: ref.nsamps_reserved)
-size_t nsamps_reserved(const Config& c, double dm) {
+// time_multiple = t rounds the valid region to 2*S*t (filterbank tscrunch)
+size_t nsamps_reserved(const Config& c, double dm, size_t time_multiple = 1) {
   if (!c.baseband_reserve_sample) return 0;
   const double f = c.baseband_freq_low + c.baseband_bandwidth;
   const double fc = c.baseband_freq_low;
@@ -50,7 +51,8 @@ size_t nsamps_reserved(const Config& c, double dm) {
       -4.148808e3 * dm * (1.0 / (f * f) - 1.0 / (fc * fc));
   const long long minimal =
       2 * (long long)std::llround(delay * c.baseband_sample_rate);
-  const long long per_bin = 2 * (long long)c.spectrum_channel_count;
+  const long long per_bin =
+      2 * (long long)c.spectrum_channel_count * (long long)time_multiple;
   const long long n = (long long)c.baseband_input_count;
   const long long refft_total = (n - minimal) / per_bin * per_bin;
   if (refft_total <= 0) {
@@ -193,7 +195,29 @@ int main(int argc, char** argv) {
   for (const double d : trial_dms)
     if (std::fabs(d) > std::fabs(reserve_dm)) reserve_dm = d;
 
-  const size_t reserved_ref = nsamps_reserved(cfg, reserve_dm);
+  // continuous filterbank output (filterbank_output_path): one DM per file
+  const bool fil_mode = !cfg.filterbank_output_path.empty();
+  if (fil_mode && trial_mode) {
+    SRTB_APP_LOGE("config: filterbank_output_path and dm_trial_list exclude "
+                  "each other (a filterbank file holds one DM)");
+    return 2;
+  }
+  if (fil_mode) {
+    const size_t t = cfg.filterbank_tscrunch, f = cfg.filterbank_fscrunch;
+    auto pow2 = [](size_t x) { return x && !(x & (x - 1)); };
+    if (!pow2(t) || t > srtb_hip::kFilterbankMaxTscrunch || !pow2(f) ||
+        cfg.spectrum_channel_count % f != 0 ||
+        (cfg.filterbank_nbits != 8 && cfg.filterbank_nbits != 32)) {
+      SRTB_APP_LOGE("config: filterbank_tscrunch must be a power of two <= "
+                    << srtb_hip::kFilterbankMaxTscrunch
+                    << ", filterbank_fscrunch a power of two dividing "
+                       "spectrum_channel_count, filterbank_nbits 8 or 32");
+      return 2;
+    }
+  }
+  const size_t fil_t = fil_mode ? cfg.filterbank_tscrunch : 1;
+
+  const size_t reserved_ref = nsamps_reserved(cfg, reserve_dm, fil_t);
   size_t reserved = reserved_ref;
   const bool udp_mode = cfg.input_file_path.empty();
   if (udp_mode && reserved > 0) {
@@ -206,7 +230,7 @@ int main(int argc, char** argv) {
     const size_t samples_per_payload =
         fmt.payload_size * 8 / (size_t)bits / (size_t)n_streams;
     const size_t step =
-        std::lcm(samples_per_payload, 2 * cfg.spectrum_channel_count);
+        std::lcm(samples_per_payload, 2 * cfg.spectrum_channel_count * fil_t);
     const size_t adj = (reserved + step - 1) / step * step;
     if (adj != reserved)
       SRTB_APP_LOGI("UDP overlap: nsamps_reserved rounded " << reserved
@@ -238,6 +262,20 @@ int main(int argc, char** argv) {
   ec.max_boxcar_length = cfg.signal_detect_max_boxcar_length;
   ec.nsamps_reserved = reserved;
   ec.max_dm_trials = (int)trial_dms.size();
+  if (fil_mode) {
+    ec.fil_tscrunch = cfg.filterbank_tscrunch;
+    ec.fil_fscrunch = cfg.filterbank_fscrunch;
+    ec.fil_nbits = cfg.filterbank_nbits;
+    const size_t per = 2 * cfg.spectrum_channel_count * fil_t;
+    if (reserved >= cfg.baseband_input_count ||
+        (cfg.baseband_input_count - reserved) % per != 0) {
+      SRTB_APP_LOGE("config: baseband_input_count - overlap ("
+                    << reserved << ") is not a positive multiple of 2 * "
+                    << "spectrum_channel_count * filterbank_tscrunch = "
+                    << per);
+      return 2;
+    }
+  }
   parse_zap_ranges(cfg, ec);
 
   // multi-GPU: one process per GPU (torchrun or shell-loop launched); the
@@ -464,6 +502,56 @@ int main(int argc, char** argv) {
                                            << " valid bytes/block)");
   }
 
+  // filterbank output: one file per data stream, header written here, block
+  // rows appended by the pool as pwrite-at-offset (like baseband_write_all)
+  std::vector<int> fil_fds;
+  size_t fil_header_len = 0, fil_block_bytes = 0;
+  uint64_t fil_index = 0, fil_delta = 0;
+  if (fil_mode) {
+    FilterbankHeader fh;
+    const double bw = std::fabs(cfg.baseband_bandwidth);
+    const size_t C = engine.filterbank_channels();
+    fh.nchans = (int)C;
+    fh.nbits = cfg.filterbank_nbits;
+    fh.foff = -bw / (double)C;
+    fh.fch1 = std::max(cfg.baseband_freq_low,
+                       cfg.baseband_freq_low + cfg.baseband_bandwidth) -
+              bw / (double)(2 * C);
+    fh.tsamp = 2.0 * (double)cfg.spectrum_channel_count *
+               (double)cfg.filterbank_tscrunch / cfg.baseband_sample_rate;
+    fh.tstart = cfg.filterbank_tstart_mjd;
+    const std::string header = filterbank_header(fh);
+    fil_header_len = header.size();
+    fil_block_bytes = engine.filterbank_rows() * C *
+                      (size_t)(cfg.filterbank_nbits / 8);
+    for (int si = 0; si < n_streams; ++si) {
+      std::string tag;
+      if (n_streams > 1) tag += "_s" + std::to_string(si);
+      if (comm.world() > 1) tag += "_r" + std::to_string(comm.rank());
+      const std::string path =
+          tag_before_extension(cfg.filterbank_output_path, tag);
+      const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+      if (fd < 0 ||
+          ::pwrite(fd, header.data(), header.size(), 0) !=
+              (ssize_t)header.size()) {
+        SRTB_APP_LOGE("cannot write " << path);
+        return 3;
+      }
+      fil_fds.push_back(fd);
+      SRTB_APP_LOGI("filterbank -> " << path << " (" << engine.filterbank_rows()
+                                     << " rows x " << C << " channels, "
+                                     << cfg.filterbank_nbits
+                                     << " bits per block)");
+    }
+    if (comm.world() > 1 && !udp_mode)
+      SRTB_APP_LOGW("filterbank: file replay over " << comm.world()
+                    << " ranks interleaves blocks, each rank's file holds "
+                       "every " << comm.world() << "th block");
+    if (udp_mode && n_endpoints > 1)
+      SRTB_APP_LOGW("filterbank: several UDP endpoints share one file per "
+                    "data stream");
+  }
+
   // async dump staging, lazily pinned on first detection
   std::vector<std::array<DumpStaging, 2>> staging(n_streams);
 
@@ -625,6 +713,37 @@ int main(int argc, char** argv) {
         res[si] = engines[si]->wait(w.slots[si]);
     }
     ++blocks;
+    if (fil_mode) {
+      // copy the rows out of the slots' pinned mirrors now (the slots are
+      // resubmitted next) and append them at this block's offset
+      if (have_last && w.counter > last_counter) {
+        const uint64_t d = w.counter - last_counter;
+        if (fil_delta == 0) fil_delta = d;
+        if (udp_mode && d != fil_delta)
+          SRTB_APP_LOGW("filterbank: block " << w.counter << " follows "
+                        << last_counter << " (step " << d << ", expected "
+                        << fil_delta << "): dropped data shortens the file");
+      }
+      const uint64_t off =
+          fil_header_len + fil_index++ * (uint64_t)fil_block_bytes;
+      for (int si = 0; si < n_streams; ++si) {
+        const uint8_t* src = static_cast<const uint8_t*>(
+            engines[si]->filterbank_host(w.slots[si]));
+        auto rows = std::make_shared<std::vector<uint8_t>>(
+            src, src + fil_block_bytes);
+        const int fd = fil_fds[si];
+        writers.post([rows, off, fd] {
+          size_t done = 0;
+          while (done < rows->size()) {
+            const ssize_t k = ::pwrite(fd, rows->data() + done,
+                                       rows->size() - done,
+                                       (off_t)(off + done));
+            if (k <= 0) break;
+            done += (size_t)k;
+          }
+        });
+      }
+    }
     if (write_all_fd >= 0) {
       // record-everything tail: append the valid region and release the
       // buffer from the pool; detections are still counted/logged below
@@ -734,6 +853,10 @@ int main(int argc, char** argv) {
     writers.drain();  // all appends on disk before fdatasync+close
     ::fdatasync(write_all_fd);
     ::close(write_all_fd);
+  }
+  if (!fil_fds.empty()) {
+    writers.drain();
+    for (const int fd : fil_fds) ::close(fd);
   }
   stop.store(true);
   for (auto& t : input_threads)

@@ -85,6 +85,59 @@ inline void write_spectrum_npy(const std::string& prefix, uint64_t counter,
   ::close(fd);
 }
 
+// sigproc filterbank header, byte-identical to the Python twin
+// srtb_amd.io.writers.filterbank_header with its default telescope_id,
+// machine_id, data_type, nifs, source_name and coordinates.
+struct FilterbankHeader {
+  double fch1 = 0, foff = 0, tsamp = 0, tstart = 0;
+  int nchans = 0, nbits = 32;
+};
+
+inline std::string filterbank_header(const FilterbankHeader& h) {
+  std::string out;
+  auto put_str = [&](const std::string& s) {
+    const int32_t n = (int32_t)s.size();
+    out.append(reinterpret_cast<const char*>(&n), 4);
+    out += s;
+  };
+  auto put_int = [&](const char* key, int32_t v) {
+    put_str(key);
+    out.append(reinterpret_cast<const char*>(&v), 4);
+  };
+  auto put_real = [&](const char* key, double v) {
+    put_str(key);
+    out.append(reinterpret_cast<const char*>(&v), 8);
+  };
+  put_str("HEADER_START");
+  put_int("telescope_id", 0);
+  put_int("machine_id", 0);
+  put_int("data_type", 1);
+  put_real("fch1", h.fch1);
+  put_real("foff", h.foff);
+  put_int("nchans", h.nchans);
+  put_real("tsamp", h.tsamp);
+  put_real("tstart", h.tstart);
+  put_int("nbits", h.nbits);
+  put_int("nifs", 1);
+  put_real("src_raj", 0.0);
+  put_real("src_dej", 0.0);
+  put_str("source_name");
+  put_str("srtb");
+  put_str("HEADER_END");
+  return out;
+}
+
+// `name.ext` -> `name<tag>.ext` (the tag goes before the extension)
+inline std::string tag_before_extension(const std::string& path,
+                                        const std::string& tag) {
+  const size_t slash = path.rfind('/');
+  size_t dot = path.rfind('.');
+  if (dot == std::string::npos ||
+      (slash != std::string::npos && dot < slash))
+    dot = path.size();
+  return path.substr(0, dot) + tag + path.substr(dot);
+}
+
 inline void write_time_series_tim(const std::string& prefix, uint64_t counter,
                                   size_t boxcar, const float* data,
                                   size_t n) {

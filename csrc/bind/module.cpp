@@ -411,6 +411,73 @@ std::vector<torch::Tensor> t_correlate(torch::Tensor f1, torch::Tensor f2,
   return {corr, mag};
 }
 
+// ---------------- filterbank output ----------------
+
+torch::Tensor t_filterbank_detect(torch::Tensor wf,
+                                  c10::optional<torch::Tensor> flags,
+                                  int64_t valid_rows, int64_t tscrunch,
+                                  int64_t fscrunch, bool reverse) {
+  CHECK_CUDA(wf);
+  CHECK_CONTIG(wf);
+  TORCH_CHECK(wf.dim() == 2 && wf.scalar_type() == torch::kComplexFloat);
+  const int64_t S = wf.size(0), L = wf.size(1);
+  TORCH_CHECK(tscrunch >= 1 && fscrunch >= 1 && S % fscrunch == 0 &&
+                  valid_rows >= tscrunch && valid_rows <= L && L % 2 == 0,
+              "filterbank_detect: bad geometry");
+  const uint8_t* f = nullptr;
+  if (flags.has_value()) {
+    CHECK_CUDA(*flags);
+    CHECK_CONTIG(*flags);
+    TORCH_CHECK(flags->scalar_type() == torch::kUInt8 && flags->numel() == S);
+    f = flags->data_ptr<uint8_t>();
+  }
+  auto out = torch::empty({valid_rows / tscrunch, S / fscrunch},
+                          wf.options().dtype(torch::kFloat32));
+  check(filterbank_detect(cptr(wf), f, S, L, valid_rows, tscrunch, fscrunch,
+                          reverse, out.data_ptr<float>(), cur_stream()),
+        "filterbank_detect");
+  return out;
+}
+
+std::vector<torch::Tensor> t_filterbank_channel_stats(torch::Tensor P) {
+  CHECK_CUDA(P);
+  CHECK_CONTIG(P);
+  TORCH_CHECK(P.dim() == 2 && P.scalar_type() == torch::kFloat32 &&
+              P.numel() > 0);
+  const int64_t R = P.size(0), C = P.size(1);
+  auto partials = torch::empty({(int64_t)filterbank_stats_partials(C)},
+                               P.options().dtype(torch::kFloat64));
+  auto mean = torch::empty({C}, P.options());
+  auto stddev = torch::empty({C}, P.options());
+  check(filterbank_channel_stats(P.data_ptr<float>(), R, C,
+                                 partials.data_ptr<double>(),
+                                 mean.data_ptr<float>(),
+                                 stddev.data_ptr<float>(), cur_stream()),
+        "filterbank_channel_stats");
+  return {mean, stddev};
+}
+
+torch::Tensor t_filterbank_quantize(torch::Tensor P, torch::Tensor mean,
+                                    torch::Tensor stddev) {
+  CHECK_CUDA(P);
+  CHECK_CONTIG(P);
+  CHECK_CUDA(mean);
+  CHECK_CONTIG(mean);
+  CHECK_CUDA(stddev);
+  CHECK_CONTIG(stddev);
+  TORCH_CHECK(P.dim() == 2 && P.scalar_type() == torch::kFloat32 &&
+              P.numel() > 0);
+  const int64_t R = P.size(0), C = P.size(1);
+  TORCH_CHECK(mean.scalar_type() == torch::kFloat32 && mean.numel() == C &&
+              stddev.scalar_type() == torch::kFloat32 && stddev.numel() == C);
+  auto out = torch::empty({R, C}, P.options().dtype(torch::kUInt8));
+  check(filterbank_quantize(P.data_ptr<float>(), mean.data_ptr<float>(),
+                            stddev.data_ptr<float>(), R, C,
+                            out.data_ptr<uint8_t>(), cur_stream()),
+        "filterbank_quantize");
+  return out;
+}
+
 // ---------------- hand-written FFT (test/bench surface) ----------------
 
 torch::Tensor t_native_fft(torch::Tensor x, int64_t sign) {
@@ -615,7 +682,8 @@ class PyEngine {
            std::vector<std::vector<int64_t>> zap_ranges, bool use_phase_table,
            bool enable_rfi_s1, bool enable_sk, int64_t n_slots,
            int64_t fft_backend, int64_t window_kind, bool use_hip_graph,
-           int64_t max_dm_trials) {
+           int64_t max_dm_trials, int64_t fil_tscrunch, int64_t fil_fscrunch,
+           int64_t fil_nbits) {
     EngineConfig c;
     c.baseband_input_count = n;
     c.baseband_input_bits = (int)nbits;
@@ -642,6 +710,11 @@ class PyEngine {
     c.window_kind = (int)window_kind;
     c.use_hip_graph = use_hip_graph;
     c.max_dm_trials = (int)max_dm_trials;
+    TORCH_CHECK(fil_tscrunch >= 0 && fil_fscrunch >= 0,
+                "fil_tscrunch and fil_fscrunch must not be negative");
+    c.fil_tscrunch = (size_t)fil_tscrunch;
+    c.fil_fscrunch = (size_t)fil_fscrunch;
+    c.fil_nbits = (int)fil_nbits;
     eng_ = std::make_unique<PipelineEngine>(c, (int)n_slots);
   }
 
@@ -781,6 +854,42 @@ class PyEngine {
     return t.clone();
   }
 
+  // [R][C] uint8 or float32: a copy of the slot's pinned mirror, complete
+  // after wait(slot)
+  torch::Tensor filterbank(int64_t slot) {
+    const auto R = (int64_t)eng_->filterbank_rows(),
+               C = (int64_t)eng_->filterbank_channels();
+    const void* p = eng_->filterbank_host((int)slot);
+    const auto dt = eng_->filterbank_nbits() == 8 ? torch::kUInt8
+                                                  : torch::kFloat32;
+    return torch::from_blob(const_cast<void*>(p), {R, C},
+                            torch::TensorOptions().dtype(dt))
+        .clone();
+  }
+
+  torch::Tensor filterbank_power(int64_t slot) {
+    return torch::from_blob(eng_->filterbank_power_ptr((int)slot),
+                            {(int64_t)eng_->filterbank_rows(),
+                             (int64_t)eng_->filterbank_channels()},
+                            torch::TensorOptions()
+                                .dtype(torch::kFloat32)
+                                .device(torch::kCUDA));
+  }
+
+  // (mean, std) per channel, CPU float32 (8-bit output only)
+  std::vector<torch::Tensor> filterbank_stats(int64_t slot) {
+    const auto C = (int64_t)eng_->filterbank_channels();
+    auto opt = torch::TensorOptions().dtype(torch::kFloat32);
+    auto mean = torch::from_blob(
+        const_cast<float*>(eng_->filterbank_mean_host((int)slot)), {C}, opt);
+    auto stddev = torch::from_blob(
+        const_cast<float*>(eng_->filterbank_std_host((int)slot)), {C}, opt);
+    return {mean.clone(), stddev.clone()};
+  }
+
+  int64_t filterbank_rows() const { return eng_->filterbank_rows(); }
+  int64_t filterbank_channels() const { return eng_->filterbank_channels(); }
+
   int64_t n() const { return eng_->n(); }
   int64_t nc() const { return eng_->nc(); }
   int64_t n_channels() const { return eng_->n_channels(); }
@@ -835,6 +944,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("generate_pixmap", &t_generate_pixmap);
   m.def("running_mean", &t_running_mean);
   m.def("correlate", &t_correlate);
+  m.def("filterbank_detect", &t_filterbank_detect, py::arg("wf"),
+        py::arg("flags"), py::arg("valid_rows"), py::arg("tscrunch"),
+        py::arg("fscrunch"), py::arg("reverse"));
+  m.def("filterbank_channel_stats", &t_filterbank_channel_stats, py::arg("P"));
+  m.def("filterbank_quantize", &t_filterbank_quantize, py::arg("P"),
+        py::arg("mean"), py::arg("std"));
   m.def("native_fft", &t_native_fft, py::arg("x"), py::arg("sign"));
   m.def("native_rfft", &t_native_rfft, py::arg("x"));
   m.def("preop_backward_fft", &t_preop_backward_fft, py::arg("spec"),
@@ -853,7 +968,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def(py::init<int64_t, int64_t, int64_t, double, double, double, double,
                     double, double, double, int64_t, int64_t,
                     std::vector<std::vector<int64_t>>, bool, bool, bool,
-                    int64_t, int64_t, int64_t, bool, int64_t>(),
+                    int64_t, int64_t, int64_t, bool, int64_t, int64_t,
+                    int64_t, int64_t>(),
            py::arg("n"), py::arg("nbits"), py::arg("channels"),
            py::arg("freq_low"), py::arg("bandwidth"), py::arg("sample_rate"),
            py::arg("dm"), py::arg("rfi_threshold") = 10.0,
@@ -864,7 +980,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("enable_rfi_s1") = true, py::arg("enable_sk") = true,
            py::arg("n_slots") = 2, py::arg("fft_backend") = 2,
            py::arg("window_kind") = 0, py::arg("use_hip_graph") = false,
-           py::arg("max_dm_trials") = 0)
+           py::arg("max_dm_trials") = 0, py::arg("fil_tscrunch") = 0,
+           py::arg("fil_fscrunch") = 1, py::arg("fil_nbits") = 32)
       .def("submit", &PyEngine::submit, py::arg("raw"),
            py::arg("dm_override") = std::nan(""))
       .def("submit_samples", &PyEngine::submit_samples, py::arg("samples"),
@@ -882,6 +999,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("waterfall", &PyEngine::waterfall)
       .def("time_series", &PyEngine::time_series)
       .def("boxcar_series", &PyEngine::boxcar_series)
+      .def("filterbank", &PyEngine::filterbank)
+      .def("filterbank_power", &PyEngine::filterbank_power)
+      .def("filterbank_stats", &PyEngine::filterbank_stats)
+      .def_property_readonly("filterbank_rows", &PyEngine::filterbank_rows)
+      .def_property_readonly("filterbank_channels",
+                             &PyEngine::filterbank_channels)
       .def_property_readonly("n", &PyEngine::n)
       .def_property_readonly("nc", &PyEngine::nc)
       .def_property_readonly("n_channels", &PyEngine::n_channels)

@@ -77,6 +77,37 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
     throw std::runtime_error("max_dm_trials must be in [0, " +
                              std::to_string(kMaxDmTrials) + "]");
 
+  if (const size_t t = cfg.fil_tscrunch) {
+    const size_t f = cfg.fil_fscrunch;
+    auto pow2 = [](size_t x) { return x && !(x & (x - 1)); };
+    if (!pow2(t) || t > kFilterbankMaxTscrunch)
+      throw std::runtime_error(
+          "filterbank: fil_tscrunch must be a power of two <= " +
+          std::to_string(kFilterbankMaxTscrunch));
+    if (!pow2(f) || s_ % f != 0)
+      throw std::runtime_error(
+          "filterbank: fil_fscrunch must be a power of two dividing the "
+          "channel count");
+    if (cfg.fil_nbits != 8 && cfg.fil_nbits != 32)
+      throw std::runtime_error("filterbank: fil_nbits must be 8 or 32");
+    if (cfg.max_dm_trials > 0)
+      throw std::runtime_error(
+          "filterbank: not together with max_dm_trials > 0 (a filterbank "
+          "holds one DM per file)");
+    if (l_ % 2 != 0)
+      throw std::runtime_error(
+          "filterbank: needs at least 2 time samples per channel");
+    if (cfg.nsamps_reserved >= n_ ||
+        (n_ - cfg.nsamps_reserved) % (2 * s_ * t) != 0)
+      throw std::runtime_error(
+          "filterbank: baseband_input_count - nsamps_reserved must be a "
+          "positive multiple of 2 * channels * fil_tscrunch = " +
+          std::to_string(2 * s_ * t));
+    fil_v_ = (n_ - cfg.nsamps_reserved) / (2 * s_);
+    fil_r_ = fil_v_ / t;
+    fil_c_ = s_ / f;
+  }
+
   const int np = reduce_partials();
   for (int i = 0; i < n_slots_; ++i) slots_.emplace_back(new Slot());
   for (auto& sp : slots_) {
@@ -140,6 +171,25 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
                 "pinned trial peak idx");
       check_hip(hipMalloc(&s.peak_scratch, detect_peaks_scratch_bytes()),
                 "peak scratch alloc");
+    }
+    if (fil_r_) {
+      const size_t cells = fil_r_ * fil_c_;
+      check_hip(hipMalloc(&s.fil_power, cells * sizeof(float)),
+                "filterbank power alloc");
+      if (cfg.fil_nbits == 8) {
+        check_hip(hipMalloc(&s.fil_stats, 2 * fil_c_ * sizeof(float)),
+                  "filterbank stats alloc");
+        check_hip(hipMalloc(&s.fil_u8, cells), "filterbank u8 alloc");
+        check_hip(hipMalloc(&s.fil_partials,
+                            filterbank_stats_partials(fil_c_) * sizeof(double)),
+                  "filterbank partials alloc");
+        check_hip(hipHostMalloc(&s.h_fil_stats, 2 * fil_c_ * sizeof(float)),
+                  "pinned filterbank stats");
+        check_hip(hipHostMalloc(&s.h_fil, cells), "pinned filterbank");
+      } else {
+        check_hip(hipHostMalloc(&s.h_fil, cells * sizeof(float)),
+                  "pinned filterbank");
+      }
     }
     // backend selection (see EngineConfig::fft_backend): the forward
     // 2^29-class packed C2C always favors the native plan; the batched
@@ -267,6 +317,14 @@ PipelineEngine::~PipelineEngine() {
       (void)hipHostFree(s.h_trial_peak_idx);
       (void)hipFree(s.peak_scratch);
     }
+    if (s.fil_power) {
+      (void)hipFree(s.fil_power);
+      if (s.fil_stats) (void)hipFree(s.fil_stats);
+      if (s.fil_u8) (void)hipFree(s.fil_u8);
+      if (s.fil_partials) (void)hipFree(s.fil_partials);
+      if (s.h_fil_stats) (void)hipHostFree(s.h_fil_stats);
+      (void)hipHostFree(s.h_fil);
+    }
     if (s.graph_exec) (void)hipGraphExecDestroy(s.graph_exec);
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -328,12 +386,47 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
   enqueue_front(s, dev_raw, dev_samples);
   enqueue_back(s, dm, plain_row(s), /*ts_dst=*/nullptr,
                /*keep_spectrum=*/false);
+  if (fil_r_) enqueue_filterbank(s);
   s.trial_dms.clear();
   s.cur_trial = -1;
   if (record_event) {
     check_hip(hipEventRecord(s.done, s.stream), "event record");
     s.busy = true;
     last_chain_done_ = s.done;
+  }
+}
+
+// Filterbank output of the block whose back half was just enqueued: one more
+// read of the waterfall's first fil_v_ columns -> power plane -> (8-bit:
+// channel statistics -> quantise) -> pinned host mirrors.  Reads the SK flags
+// directly, so the waterfall stays un-zapped (see enqueue_back step 6).
+void PipelineEngine::enqueue_filterbank(Slot& s) {
+  hipStream_t st = s.stream;
+  const size_t cells = fil_r_ * fil_c_;
+  check_hip(filterbank_detect(s.wf, cfg_.enable_sk ? s.flags : nullptr, s_, l_,
+                              fil_v_, cfg_.fil_tscrunch, cfg_.fil_fscrunch,
+                              /*reverse=*/cfg_.bandwidth > 0, s.fil_power, st),
+            "filterbank detect");
+  if (cfg_.fil_nbits == 8) {
+    float* mean = s.fil_stats;
+    float* stddev = s.fil_stats + fil_c_;
+    check_hip(filterbank_channel_stats(s.fil_power, fil_r_, fil_c_,
+                                       s.fil_partials, mean, stddev, st),
+              "filterbank stats");
+    check_hip(filterbank_quantize(s.fil_power, mean, stddev, fil_r_, fil_c_,
+                                  s.fil_u8, st),
+              "filterbank quantize");
+    check_hip(hipMemcpyAsync(s.h_fil, s.fil_u8, cells, hipMemcpyDeviceToHost,
+                             st),
+              "filterbank d2h");
+    check_hip(hipMemcpyAsync(s.h_fil_stats, s.fil_stats,
+                             2 * fil_c_ * sizeof(float), hipMemcpyDeviceToHost,
+                             st),
+              "filterbank stats d2h");
+  } else {
+    check_hip(hipMemcpyAsync(s.h_fil, s.fil_power, cells * sizeof(float),
+                             hipMemcpyDeviceToHost, st),
+              "filterbank d2h");
   }
 }
 
@@ -848,6 +941,29 @@ float2* PipelineEngine::waterfall_ptr(int slot) {
 float* PipelineEngine::time_series_ptr(int slot) { return slots_.at(slot)->ts; }
 float* PipelineEngine::cumsum_ptr(int slot) { return slots_.at(slot)->cumsum; }
 hipStream_t PipelineEngine::stream(int slot) { return slots_.at(slot)->stream; }
+
+const void* PipelineEngine::filterbank_host(int slot) {
+  Slot& s = *slots_.at(slot);
+  if (!s.h_fil) throw std::runtime_error("filterbank: fil_tscrunch = 0");
+  return s.h_fil;
+}
+
+float* PipelineEngine::filterbank_power_ptr(int slot) {
+  Slot& s = *slots_.at(slot);
+  if (!s.fil_power) throw std::runtime_error("filterbank: fil_tscrunch = 0");
+  return s.fil_power;
+}
+
+const float* PipelineEngine::filterbank_mean_host(int slot) {
+  Slot& s = *slots_.at(slot);
+  if (!s.h_fil_stats)
+    throw std::runtime_error("filterbank: statistics exist only at 8 bits");
+  return s.h_fil_stats;
+}
+
+const float* PipelineEngine::filterbank_std_host(int slot) {
+  return filterbank_mean_host(slot) + fil_c_;
+}
 
 float* PipelineEngine::compute_boxcar(int slot, size_t L) {
   float* box = compute_boxcar_async(slot, L);

@@ -8,7 +8,8 @@
 //   batched backward C2C (waterfall) → SK row stats → flags → zap rows →
 //   time series → baseline subtract → threshold counts → prefix scan →
 //   boxcar ladder (2,4,…,max) with per-length thresholds →
-//   D2H(result counters) → event
+//   D2H(result counters) → [filterbank: detect → stats → quantise → D2H] →
+//   event
 //
 // Two slots, each with its own HIP stream, device buffers and hipFFT plans:
 // while slot A computes, slot B's next block uploads (the reference instead
@@ -65,6 +66,16 @@ struct EngineConfig {
   // T > 0 adds per slot one [Nc] work buffer, a [T][ts_count] DM-time plane
   // and T result rows.  At most kMaxDmTrials.
   int max_dm_trials = 0;
+  // Filterbank output (docs/ARCHITECTURE.md): every block's waterfall is
+  // reduced to a [R][C] power plane that lands in pinned host memory before
+  // the slot's `done` event.  fil_tscrunch = 0 = off, nothing is allocated.
+  // tscrunch, fscrunch: powers of two, tscrunch <= 4096, fscrunch divides S;
+  // (N - nsamps_reserved) must be a multiple of 2*S*tscrunch.  nbits: 8
+  // (per-block, per-channel normalised uint8) or 32 (float power).  Not
+  // together with max_dm_trials > 0.
+  size_t fil_tscrunch = 0;
+  size_t fil_fscrunch = 1;
+  int fil_nbits = 32;
 };
 
 constexpr int kMaxDmTrials = 256;
@@ -187,6 +198,19 @@ class PipelineEngine {
 
   hipStream_t stream(int slot);
 
+  // Filterbank output (fil_tscrunch > 0; otherwise rows = channels = 0 and
+  // the pointer accessors throw).  The host pointers are the slot's pinned
+  // mirrors, complete after wait(slot) and valid until the slot is submitted
+  // again: filterbank_host = [rows][channels] uint8 or float, mean/std =
+  // [channels] float (8-bit only).
+  size_t filterbank_rows() const { return fil_r_; }
+  size_t filterbank_channels() const { return fil_c_; }
+  int filterbank_nbits() const { return fil_r_ ? cfg_.fil_nbits : 0; }
+  const void* filterbank_host(int slot);
+  float* filterbank_power_ptr(int slot);  // device [rows][channels]
+  const float* filterbank_mean_host(int slot);
+  const float* filterbank_std_host(int slot);
+
  private:
   struct Slot;
   // where one backward half leaves its counters and thresholds
@@ -214,9 +238,12 @@ class PipelineEngine {
                       int n_trials);
   void enqueue_trial(Slot& s, int k);
   void check_trials(int n_trials) const;
+  void enqueue_filterbank(Slot& s);
 
   EngineConfig cfg_;
   size_t n_, nc_, s_, l_, ts_count_, raw_bytes_;
+  // filterbank geometry: valid waterfall columns, output rows and channels
+  size_t fil_v_ = 0, fil_r_ = 0, fil_c_ = 0;
   int n_boxcars_ = 0;
   std::vector<size_t> boxcar_lengths_;
   float sk_lo_ = 0, sk_hi_ = 0;
@@ -282,6 +309,13 @@ class PipelineEngine {
     std::vector<double> trial_dms;  // of the last trial submission
     int cur_trial = -1;             // trial whose products the slot holds
     ResultRow last_row;             // row of the back half most recently run
+    // filterbank state (allocated only with fil_tscrunch > 0)
+    float* fil_power = nullptr;       // [R][C]
+    float* fil_stats = nullptr;       // [2][C] mean, std (8-bit)
+    uint8_t* fil_u8 = nullptr;        // [R][C] (8-bit)
+    double* fil_partials = nullptr;   // stats scratch (8-bit)
+    void* h_fil = nullptr;            // pinned mirror of the output plane
+    float* h_fil_stats = nullptr;     // pinned [2][C] (8-bit)
   };
   std::vector<std::unique_ptr<Slot>> slots_;
   int next_slot_ = 0;

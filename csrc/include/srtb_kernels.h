@@ -203,6 +203,39 @@ hipError_t detect_peaks(const float* ts, const float* cumsum, size_t ts_count,
                         float* out_value, unsigned* out_index,
                         hipStream_t stream);
 
+// ---------------- filterbank output (csrc/kernels/filterbank.hip) ----------
+// Definition: docs/ARCHITECTURE.md, "Filterbank output".
+constexpr size_t kFilterbankMaxTscrunch = 4096;
+constexpr int kFilterbankQuantLevel = 64;     // 8-bit level of the mean
+constexpr int kFilterbankQuantPerSigma = 16;  // 8-bit levels per sigma
+
+// out[r][c] (R = V / tscrunch rows, C = S / fscrunch channels, c fastest) =
+// sum of |wf[row][t]|^2 over the cell's fscrunch waterfall rows and tscrunch
+// time samples, taken from the first V columns of the [S][L] waterfall.
+// Output channel c holds rows c*fscrunch ... (reverse = false) or
+// S-(c+1)*fscrunch ... (reverse = true).  Rows with flags[row] != 0
+// contribute 0; flags may be null.  One pass, no atomics, bit-identical from
+// run to run.  tscrunch: power of two <= kFilterbankMaxTscrunch, fscrunch
+// divides S, tscrunch <= V <= L, L even (rows are read as float4).
+hipError_t filterbank_detect(const float2* wf, const uint8_t* flags, size_t S,
+                             size_t L, size_t V, size_t tscrunch,
+                             size_t fscrunch, bool reverse, float* out,
+                             hipStream_t stream);
+
+// Per-channel mean and (population) standard deviation of P[R][C], two-stage
+// with fp64 partials combined in fixed order, stored as float.  partials:
+// device scratch of filterbank_stats_partials(C) doubles.
+size_t filterbank_stats_partials(size_t C);
+hipError_t filterbank_channel_stats(const float* P, size_t R, size_t C,
+                                    double* partials, float* mean,
+                                    float* stddev, hipStream_t stream);
+
+// out[r][c] = clamp(rint((P - mean_c) * (16 / std_c) + 64), 0, 255) in fp32;
+// 64 where std_c = 0.
+hipError_t filterbank_quantize(const float* P, const float* mean,
+                               const float* stddev, size_t R, size_t C,
+                               uint8_t* out_u8, hipStream_t stream);
+
 // ---------------- hand-written Stockham FFT ----------------
 // One generic pass of the LDS-staged Stockham FFT (csrc/kernels/fft.hip).
 // Index-math oracle: srtb_amd/fftref.py.  Host-side planning:

@@ -28,6 +28,7 @@ HIP_SOURCES = [
     "csrc/kernels/spectrum.hip",
     "csrc/kernels/display.hip",
     "csrc/kernels/fft.hip",
+    "csrc/kernels/filterbank.hip",
     "csrc/engine/engine.cpp",
 ]
 

@@ -55,6 +55,11 @@ _FIELD_KINDS = {
     "gui_pixmap_width": "int",
     "gui_pixmap_height": "int",
     "log_level": "int",
+    "filterbank_output_path": "str",
+    "filterbank_tscrunch": "int",
+    "filterbank_fscrunch": "int",
+    "filterbank_nbits": "int",
+    "filterbank_tstart_mjd": "real",
 }
 
 
@@ -94,6 +99,14 @@ class Config:
     gui_pixmap_width: int = 1920
     gui_pixmap_height: int = 1080
     log_level: int = 3
+    # continuous SIGPROC filterbank output: "" = off; time / frequency scrunch
+    # factors (powers of two), 8 or 32 bits per sample, start time for the
+    # header
+    filterbank_output_path: str = ""
+    filterbank_tscrunch: int = 16
+    filterbank_fscrunch: int = 1
+    filterbank_nbits: int = 8
+    filterbank_tstart_mjd: float = 0.0
 
     # ---- assignment from strings (expression values) ----
 

@@ -226,3 +226,97 @@ def write_filterbank(path: str, header: bytes, data: np.ndarray) -> None:
     with open(path, "wb") as f:
         f.write(header)
         f.write(np.asarray(data, dtype=np.float32).tobytes())
+
+
+class FilterbankWriter:
+    """Continuous sigproc .fil stream: the header is written once, then
+    blocks of [rows][nchans] samples (uint8 for nbits = 8, float32 for
+    nbits = 32) are appended in call order.
+
+    header_kwargs: the keyword arguments of :func:`filterbank_header`."""
+
+    def __init__(self, path: str, header_kwargs: dict):
+        self.path = path
+        self.nchans = int(header_kwargs["nchans"])
+        self.nbits = int(header_kwargs.get("nbits", 32))
+        if self.nbits not in (8, 32):
+            raise ValueError("FilterbankWriter: nbits must be 8 or 32")
+        self.dtype = np.uint8 if self.nbits == 8 else np.float32
+        self.rows = 0
+        self._f = open(path, "wb")
+        self._f.write(filterbank_header(**header_kwargs))
+
+    def append(self, block: np.ndarray) -> None:
+        block = np.asarray(block)
+        if block.ndim != 2 or block.shape[1] != self.nchans:
+            raise ValueError(
+                f"FilterbankWriter: block shape {block.shape}, expected "
+                f"[rows][{self.nchans}]")
+        if block.dtype != self.dtype:
+            raise ValueError(
+                f"FilterbankWriter: block dtype {block.dtype}, the file holds "
+                f"{np.dtype(self.dtype)}")
+        self._f.write(np.ascontiguousarray(block).tobytes())
+        self.rows += block.shape[0]
+
+    def close(self) -> None:
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+_HEADER_INT_KEYS = {"telescope_id", "machine_id", "data_type", "nchans",
+                    "nbits", "nifs", "nbeams", "ibeam", "barycentric",
+                    "pulsarcentric", "nsamples"}
+_HEADER_STR_KEYS = {"source_name", "rawdatafile"}
+
+
+def read_filterbank(path: str) -> tuple[dict, np.ndarray]:
+    """Read a sigproc .fil file written with nbits 8 or 32.  Returns the
+    header as a dict (plus ``header_len``, its size in bytes) and the data as
+    a [rows][nchans] uint8 or float32 array."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    pos = 0
+
+    def take_string() -> str:
+        nonlocal pos
+        (n,) = struct.unpack_from("<i", buf, pos)
+        if not 0 < n <= 80:
+            raise ValueError(f"{path}: malformed filterbank header")
+        pos += 4
+        s = buf[pos:pos + n].decode()
+        pos += n
+        return s
+
+    if take_string() != "HEADER_START":
+        raise ValueError(f"{path}: not a sigproc filterbank file")
+    header: dict = {}
+    while True:
+        key = take_string()
+        if key == "HEADER_END":
+            break
+        if key in _HEADER_STR_KEYS:
+            header[key] = take_string()
+        elif key in _HEADER_INT_KEYS:
+            (header[key],) = struct.unpack_from("<i", buf, pos)
+            pos += 4
+        else:
+            (header[key],) = struct.unpack_from("<d", buf, pos)
+            pos += 8
+    header["header_len"] = pos
+    nbits = header.get("nbits", 32)
+    if nbits not in (8, 32):
+        raise ValueError(f"{path}: nbits = {nbits} is not supported")
+    dtype = np.uint8 if nbits == 8 else np.float32
+    nchans = header["nchans"]
+    rows = (len(buf) - pos) // (np.dtype(dtype).itemsize * nchans)
+    data = np.frombuffer(buf, dtype=dtype, offset=pos, count=rows * nchans)
+    return header, data.reshape(rows, nchans).copy()

@@ -28,7 +28,8 @@ from . import ref
 from .config import Config, parse_args
 from .io import backends as bk
 from .io.file_input import FileBlockReader
-from .io.writers import BlockProducts, SignalWriteScheduler
+from .io.writers import (BlockProducts, FilterbankWriter,
+                         SignalWriteScheduler)
 from .pipeline.cpu import CpuPipeline
 from .parallel.sharding import (DetectionAggregator, broadcast_config,
                                 init_distributed, shard_streams)
@@ -48,6 +49,53 @@ def write_ppm(path: str, argb: np.ndarray) -> None:
     with open(path, "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (w, h))
         f.write(rgb.tobytes())
+
+
+def filterbank_time_multiple(cfg: Config) -> int:
+    """The overlap's extra rounding factor: tscrunch while the filterbank
+    output is on, so a block's valid waterfall columns are whole output rows."""
+    return cfg.filterbank_tscrunch if cfg.filterbank_output_path else 1
+
+
+def filterbank_paths(cfg: Config, n_streams: int, rank: int, world: int,
+                     endpoint: int | None = None) -> list[str]:
+    """One output file per data stream: ``_s{k}`` goes before the extension
+    for multi-stream formats, ``_r{rank}`` when several ranks run, ``_e{i}``
+    when one rank serves several UDP endpoints."""
+    path = cfg.filterbank_output_path
+    dot = path.rfind(".")
+    if dot <= path.rfind("/"):
+        dot = len(path)
+    stem, ext = path[:dot], path[dot:]
+    tag = f"_r{rank}" if world > 1 else ""
+    if endpoint is not None:
+        tag += f"_e{endpoint}"
+    return [stem + (f"_s{k}" if n_streams > 1 else "") + tag + ext
+            for k in range(n_streams)]
+
+
+def filterbank_header_kwargs(cfg: Config) -> dict:
+    kw = ref.filterbank_header_fields(
+        cfg.baseband_freq_low, cfg.baseband_bandwidth,
+        cfg.baseband_sample_rate, cfg.spectrum_channel_count,
+        cfg.filterbank_tscrunch, cfg.filterbank_fscrunch)
+    kw.update(nbits=cfg.filterbank_nbits, tstart=cfg.filterbank_tstart_mjd)
+    return kw
+
+
+def cpu_filterbank_block(cfg: Config, wf: np.ndarray,
+                         nsamps_reserved: int) -> np.ndarray:
+    """The engine's filterbank rows of one block from the oracle functions
+    (wf: the SK-zapped waterfall)."""
+    valid = ref.filterbank_valid_rows(cfg.baseband_input_count, wf.shape[0],
+                                      nsamps_reserved)
+    power = ref.filterbank_block(
+        wf, valid, cfg.filterbank_tscrunch, cfg.filterbank_fscrunch,
+        reverse=cfg.baseband_bandwidth > 0).astype(np.float32)
+    if cfg.filterbank_nbits == 32:
+        return power
+    mean, std = ref.filterbank_channel_stats(power)
+    return ref.filterbank_quantize(power, mean, std)
 
 
 def _engine_products(eng, cfg: Config, slot: int, res: dict,
@@ -79,6 +127,7 @@ class GpuStreamPipeline:
     def __init__(self, cfg: Config, nsamps_reserved: int):
         import torch
         from .ops import native
+        from .pipeline.gpu import filterbank_engine_kwargs
         self.torch = torch
         self.C = native()
         self.cfg = cfg
@@ -98,7 +147,10 @@ class GpuStreamPipeline:
             nsamps_reserved=nsamps_reserved,
             zap_ranges=[[int(a), int(b)] for a, b in bins],
             use_phase_table=False, enable_rfi_s1=True, enable_sk=True,
-            n_slots=2)
+            n_slots=2, **filterbank_engine_kwargs(cfg))
+
+    def filterbank_blocks(self) -> list[np.ndarray]:
+        return [self.eng.filterbank(self.last_slot).numpy()]
 
     def process_block(self, raw: np.ndarray, counter: int) -> BlockProducts:
         torch = self.torch
@@ -132,14 +184,19 @@ class GpuMultiPolPipeline:
     def __init__(self, cfg: Config, nsamps_reserved: int, fmt_name: str):
         import torch
         from .ops import native
-        from .pipeline.gpu import _make_engine
+        from .pipeline.gpu import _make_engine, filterbank_engine_kwargs
         self.torch = torch
         self.C = native()
         self.cfg = cfg
         self.fmt = bk.resolve_alias(fmt_name)
         self.n_streams = bk.get_data_stream_count(fmt_name)
-        self.engines = [_make_engine(self.C, cfg, nsamps_reserved, nbits=-8)
+        self.engines = [_make_engine(self.C, cfg, nsamps_reserved, nbits=-8,
+                                     **filterbank_engine_kwargs(cfg))
                         for _ in range(self.n_streams)]
+
+    def filterbank_blocks(self) -> list[np.ndarray]:
+        return [e.filterbank(s).numpy()
+                for e, s in zip(self.engines, self.last_slots)]
 
     def _fanout(self, raw_t):
         if self.fmt == "gznupsr_a1":
@@ -201,7 +258,14 @@ class CpuMultiPolPipeline:
         self.cfg = cfg
         self.fmt = bk.resolve_alias(fmt_name)
         self.n_streams = bk.get_data_stream_count(fmt_name)
-        self.pipes = [CpuPipeline(cfg) for _ in range(self.n_streams)]
+        self.nsamps_reserved = nsamps_reserved
+        self.pipes = [CpuPipeline(cfg, nsamps_reserved)
+                      for _ in range(self.n_streams)]
+
+    def filterbank_blocks(self) -> list[np.ndarray]:
+        return [cpu_filterbank_block(self.cfg, r["waterfall"],
+                                     self.nsamps_reserved)
+                for r in self.last_results]
 
     def _fanout(self, raw: np.ndarray) -> list[np.ndarray]:
         if self.fmt == "gznupsr_a1":
@@ -254,7 +318,12 @@ class CpuStreamPipeline:
 
     def __init__(self, cfg: Config, nsamps_reserved: int):
         self.cfg = cfg
-        self.pipe = CpuPipeline(cfg)
+        self.nsamps_reserved = nsamps_reserved
+        self.pipe = CpuPipeline(cfg, nsamps_reserved)
+
+    def filterbank_blocks(self) -> list[np.ndarray]:
+        return [cpu_filterbank_block(self.cfg, self.last_result["waterfall"],
+                                     self.nsamps_reserved)]
 
     def process_block(self, raw: np.ndarray, counter: int) -> BlockProducts:
         cfg = self.cfg
@@ -315,6 +384,20 @@ def main(argv=None) -> int:
     cfg = parse_args(cfg_argv) if rank == 0 else Config()
     cfg = broadcast_config(cfg if rank == 0 else None)
 
+    if cfg.filterbank_output_path:
+        if cfg.dm_trial_list.strip():
+            raise SystemExit(
+                "config: filterbank_output_path and dm_trial_list exclude each "
+                "other (a filterbank file holds one DM)")
+        t, f = cfg.filterbank_tscrunch, cfg.filterbank_fscrunch
+        s_ = cfg.spectrum_channel_count
+        if (t < 1 or t & (t - 1) or t > 4096 or f < 1 or f & (f - 1)
+                or s_ % f or cfg.filterbank_nbits not in (8, 32)):
+            raise SystemExit(
+                "config: filterbank_tscrunch must be a power of two <= 4096, "
+                "filterbank_fscrunch a power of two dividing "
+                "spectrum_channel_count, filterbank_nbits 8 or 32")
+
     import importlib
     torch_spec = importlib.util.find_spec("torch")
     use_gpu = False
@@ -325,7 +408,8 @@ def main(argv=None) -> int:
     reserved = ref.nsamps_reserved(
         cfg.baseband_input_count, cfg.spectrum_channel_count,
         cfg.baseband_freq_low, cfg.baseband_bandwidth,
-        cfg.baseband_sample_rate, cfg.dm, cfg.baseband_reserve_sample)
+        cfg.baseband_sample_rate, cfg.dm, cfg.baseband_reserve_sample,
+        time_multiple=filterbank_time_multiple(cfg))
 
     # polarization fan-out: formats with >1 data stream run one packed
     # packet stream through per-pol pipelines + cross-pol coincidence writes
@@ -378,6 +462,29 @@ def main(argv=None) -> int:
         cfg.baseband_sample_rate, real_time=(cfg.input_file_path == ""),
         async_writes=True)
 
+    # continuous filterbank output: one file per data stream (and endpoint)
+    fil_writers: dict = {}
+
+    def fil_append(pipe, ep=None, n_eps=1):
+        if not cfg.filterbank_output_path:
+            return
+        if ep not in fil_writers:
+            paths = filterbank_paths(cfg, n_streams, rank, world,
+                                     endpoint=ep if n_eps > 1 else None)
+            fil_writers[ep] = [FilterbankWriter(
+                p_, filterbank_header_kwargs(cfg)) for p_ in paths]
+        for w, rows in zip(fil_writers[ep], pipe.filterbank_blocks()):
+            w.append(rows)
+
+    if cfg.filterbank_output_path:
+        valid = cfg.baseband_input_count - reserved
+        per = 2 * cfg.spectrum_channel_count * cfg.filterbank_tscrunch
+        if valid <= 0 or valid % per:
+            raise SystemExit(
+                f"config: baseband_input_count - overlap = {valid} is not a "
+                f"positive multiple of 2 * spectrum_channel_count * "
+                f"filterbank_tscrunch = {per}")
+
     t0 = time.time()
     n_blocks = 0
     # baseband_write_all: record every block (minus the overlap tail) into
@@ -399,6 +506,7 @@ def main(argv=None) -> int:
         for sample_index, raw in reader:
             for products in process(pipe, raw, sample_index):
                 writer.push(products)
+            fil_append(pipe)
             if write_all_f is not None:
                 end = raw.size - reserved_bytes if reserved_bytes else raw.size
                 write_all_f.write(raw[:end].tobytes())
@@ -464,6 +572,7 @@ def main(argv=None) -> int:
                 continue
             for products in process(pipes[ep], blk, ts):
                 writer.push(products)
+            fil_append(pipes[ep], ep, len(my))
             state["n"] += 1
             gui_update(pipes[ep], state["n"], len(writer.written))
         state["stop"] = True
@@ -471,6 +580,9 @@ def main(argv=None) -> int:
 
     if write_all_f is not None:
         write_all_f.close()
+    for ws in fil_writers.values():
+        for w in ws:
+            w.close()
     elapsed = time.time() - t0
     if gui is not None:
         # keep serving the last frames briefly (the reference GUI keeps its

@@ -24,12 +24,17 @@ from ..config import Config
 class CpuPipeline:
     """Single-stream, single-block-at-a-time CPU pipeline."""
 
-    def __init__(self, cfg: Config):
+    def __init__(self, cfg: Config, nsamps_reserved: int | None = None):
         self.cfg = cfg
         self.rfi_ranges = ref.parse_rfi_freq_list(cfg.mitigate_rfi_freq_list)
         self.window_kind = "rectangle"  # reference default_window
+        # overlap chosen by the caller (e.g. rounded for the filterbank's
+        # tscrunch); None = derive it from the config
+        self._nsamps_reserved = nsamps_reserved
 
     def nsamps_reserved(self) -> int:
+        if self._nsamps_reserved is not None:
+            return self._nsamps_reserved
         c = self.cfg
         return ref.nsamps_reserved(
             c.baseband_input_count, c.spectrum_channel_count,
@@ -92,11 +97,17 @@ class CpuPipeline:
 
 def synthesize_dispersed_pulse(cfg: Config, pulse_t: float, pulse_amp: float,
                                noise_sigma: float = 1.0,
-                               rng: np.random.Generator | None = None) -> np.ndarray:
+                               rng: np.random.Generator | None = None,
+                               width: int = 32) -> np.ndarray:
     """Synthesize one block of 8-bit baseband containing Gaussian noise plus a
     dispersed impulse at time ``pulse_t`` (seconds into the block) with the
     config's DM — built in the frequency domain with the *inverse* of the
     dedispersion phase so the pipeline's dedispersion exactly re-aligns it.
+
+    ``width``: half-width of the click in samples (Gaussian of sigma
+    width / 4).  The default click is smooth, so its power sits in the few MHz
+    next to ``baseband_freq_low``; width = 1 is a near-delta that fills the
+    whole band.
 
     Returns a uint8/int8 packed byte array of the config's bit width.
     """
@@ -109,7 +120,6 @@ def synthesize_dispersed_pulse(cfg: Config, pulse_t: float, pulse_amp: float,
     idx = int(pulse_t * c.baseband_sample_rate)
     idx = max(0, min(n - 1, idx))
     # a short wideband pulse (few samples wide, smoothed)
-    width = 32
     t = np.arange(-width, width + 1)
     x[np.clip(idx + t, 0, n - 1)] += np.exp(-0.5 * (t / (width / 4)) ** 2)
 

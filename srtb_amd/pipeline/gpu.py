@@ -21,9 +21,19 @@ from .. import ref
 from ..config import Config
 
 
+def filterbank_engine_kwargs(cfg: Config) -> dict:
+    """Engine keywords that switch the filterbank output on ({} while
+    ``filterbank_output_path`` is unset)."""
+    if not cfg.filterbank_output_path:
+        return {}
+    return {"fil_tscrunch": cfg.filterbank_tscrunch,
+            "fil_fscrunch": cfg.filterbank_fscrunch,
+            "fil_nbits": cfg.filterbank_nbits}
+
+
 def _make_engine(C, cfg: Config, nsamps_reserved: int, nbits: int,
                  n: int | None = None, n_slots: int = 2,
-                 max_dm_trials: int = 0):
+                 max_dm_trials: int = 0, **engine_kwargs):
     nc = (n or cfg.baseband_input_count) // 2
     ranges = ref.parse_rfi_freq_list(cfg.mitigate_rfi_freq_list)
     bins = ref.rfi_ranges_to_bins(cfg.baseband_freq_low,
@@ -39,7 +49,7 @@ def _make_engine(C, cfg: Config, nsamps_reserved: int, nbits: int,
         nsamps_reserved=nsamps_reserved,
         zap_ranges=[[int(a), int(b)] for a, b in bins],
         use_phase_table=False, enable_rfi_s1=True, enable_sk=True,
-        n_slots=n_slots, max_dm_trials=max_dm_trials)
+        n_slots=n_slots, max_dm_trials=max_dm_trials, **engine_kwargs)
 
 
 class DualPolPipeline:

@@ -252,15 +252,19 @@ def dispersion_delay_time(f: float, f_c: float, dm: float) -> float:
 
 def nsamps_reserved(baseband_input_count: int, spectrum_channel_count: int,
                     freq_low: float, bandwidth: float, sample_rate: float,
-                    dm: float, reserve: bool = True) -> int:
+                    dm: float, reserve: bool = True,
+                    time_multiple: int = 1) -> int:
     """Overlap (in real samples) between adjacent blocks so dedispersion edge
     garbage can be dropped; the valid region is rounded down to a multiple of
-    2 * spectrum_channel_count (reference coherent_dedispersion.hpp:87-128)."""
+    2 * spectrum_channel_count (reference coherent_dedispersion.hpp:87-128).
+    ``time_multiple`` = t rounds it down to a multiple of
+    2 * spectrum_channel_count * t instead, so that the valid waterfall
+    columns of a block divide into whole groups of t (filterbank tscrunch)."""
     if not reserve:
         return 0
     max_delay = dispersion_delay_time(freq_low + bandwidth, freq_low, dm)
     minimal = 2 * round(max_delay * sample_rate)
-    per_bin = 2 * spectrum_channel_count
+    per_bin = 2 * spectrum_channel_count * time_multiple
     refft_total = (baseband_input_count - minimal) // per_bin * per_bin
     n_may = baseband_input_count - refft_total
     if refft_total > 0:
@@ -410,6 +414,83 @@ def detect_signals(wf: np.ndarray, nsamps_reserved_real: int,
             L *= 2
     return {"time_series": ts, "zero_count": zero_count,
             "detections": detections}
+
+
+# ---------------------------------------------------------------------------
+# Filterbank output (no reference counterpart: its
+# frequency_domain_filterbank_queue is a TODO; definition in
+# docs/ARCHITECTURE.md, "Filterbank output")
+# ---------------------------------------------------------------------------
+
+FILTERBANK_QUANT_LEVEL = 64      # 8-bit level of a channel's mean
+FILTERBANK_QUANT_PER_SIGMA = 16  # 8-bit levels per standard deviation
+
+
+def filterbank_valid_rows(baseband_input_count: int,
+                          spectrum_channel_count: int,
+                          nsamps_reserved_real: int) -> int:
+    """Waterfall time samples of a block that the next block does not repeat:
+    V = (N - nsamps_reserved) / (2 S)."""
+    return ((baseband_input_count - nsamps_reserved_real)
+            // (2 * spectrum_channel_count))
+
+
+def filterbank_block(wf: np.ndarray, valid_rows: int, tscrunch: int,
+                     fscrunch: int, reverse: bool) -> np.ndarray:
+    """Power plane P[R][C] (float64, time-major, channel fastest) of one
+    [S][L] waterfall: R = valid_rows // tscrunch, C = S // fscrunch,
+    P[r][c] = sum of |wf[row][t]|^2 over the cell's fscrunch rows and tscrunch
+    time samples of the first ``valid_rows`` columns.  Output channel c holds
+    rows c*fscrunch ... (reverse=False) or S-(c+1)*fscrunch ... (reverse=True,
+    used for positive bandwidth so that channels run in descending
+    frequency).  Zapped (all-zero) rows contribute 0 by themselves."""
+    wf = np.asarray(wf)
+    S, L = wf.shape
+    if S % fscrunch != 0 or not 0 < tscrunch <= valid_rows <= L:
+        raise ValueError("filterbank_block: bad geometry")
+    R, C = valid_rows // tscrunch, S // fscrunch
+    p = (wf.real.astype(np.float64) ** 2 + wf.imag.astype(np.float64) ** 2)
+    p = p[:, :R * tscrunch].reshape(C, fscrunch, R, tscrunch).sum(axis=(1, 3))
+    if reverse:
+        p = p[::-1]
+    return np.ascontiguousarray(p.T)
+
+
+def filterbank_quantize(P: np.ndarray, mean: np.ndarray,
+                        std: np.ndarray) -> np.ndarray:
+    """q = clamp(rint((P - mean_c) * (16 / std_c) + 64), 0, 255) per channel
+    (columns of P), 64 where std_c = 0; evaluated in float64."""
+    P = np.asarray(P, dtype=np.float64)
+    mean = np.asarray(mean, dtype=np.float64)
+    std = np.asarray(std, dtype=np.float64)
+    ok = std > 0
+    scale = np.where(ok, FILTERBANK_QUANT_PER_SIGMA / np.where(ok, std, 1.0),
+                     0.0)
+    q = np.rint((P - mean[None, :]) * scale[None, :] + FILTERBANK_QUANT_LEVEL)
+    q = np.where(ok[None, :], q, float(FILTERBANK_QUANT_LEVEL))
+    return np.clip(q, 0, 255).astype(np.uint8)
+
+
+def filterbank_channel_stats(P: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Per-channel mean and population standard deviation of P[R][C],
+    accumulated in float64 and stored as float32."""
+    P = np.asarray(P, dtype=np.float64)
+    return P.mean(axis=0).astype(np.float32), P.std(axis=0).astype(np.float32)
+
+
+def filterbank_header_fields(freq_low: float, bandwidth: float,
+                             sample_rate: float, spectrum_channel_count: int,
+                             tscrunch: int, fscrunch: int) -> dict:
+    """fch1 / foff / tsamp / nchans of the filterbank file (channels in
+    descending frequency, fch1 = centre of the highest channel)."""
+    C = spectrum_channel_count // fscrunch
+    bw = abs(bandwidth)
+    return {
+        "fch1": max(freq_low, freq_low + bandwidth) - bw / (2 * C),
+        "foff": -bw / C,
+        "nchans": C,
+        "tsamp": 2.0 * spectrum_channel_count * tscrunch / sample_rate,
+    }
 
 
 # ---------------------------------------------------------------------------
