@@ -210,6 +210,15 @@ struct Config {
   size_t filterbank_fscrunch = 1;
   int filterbank_nbits = 8;
   double filterbank_tstart_mjd = 0.0;
+  // pulsar folding ("" = off), twin of the Python keys: period (s), its
+  // derivative (s/s), phase bins, phase (turns) at stream sample 0, blocks
+  // per sub-integration (0 = one for the whole run)
+  std::string fold_output_path;
+  double fold_period = 0.0;
+  double fold_period_derivative = 0.0;
+  size_t fold_nbin = 256;
+  double fold_phase_offset = 0.0;
+  size_t fold_subint_blocks = 0;
 
   void assign(const std::string& key, const std::string& raw);
   void parse_file(const std::string& path);
@@ -284,6 +293,12 @@ inline void Config::assign(const std::string& key, const std::string& raw0) {
   else if (key == "filterbank_fscrunch") filterbank_fscrunch = I();
   else if (key == "filterbank_nbits") filterbank_nbits = (int)Expr::eval_int(raw);
   else if (key == "filterbank_tstart_mjd") filterbank_tstart_mjd = D();
+  else if (key == "fold_output_path") fold_output_path = raw;
+  else if (key == "fold_period") fold_period = D();
+  else if (key == "fold_period_derivative") fold_period_derivative = D();
+  else if (key == "fold_nbin") fold_nbin = I();
+  else if (key == "fold_phase_offset") fold_phase_offset = D();
+  else if (key == "fold_subint_blocks") fold_subint_blocks = I();
   else throw std::runtime_error("unknown config key: " + key);
 }
 
@@ -365,6 +380,16 @@ inline std::string Config::dump() const {
       << "filterbank_fscrunch = " << filterbank_fscrunch << "\n"
       << "filterbank_nbits = " << filterbank_nbits << "\n"
       << "filterbank_tstart_mjd = " << filterbank_tstart_mjd << "\n";
+    o.precision(prec);
+  }
+  if (!fold_output_path.empty()) {
+    const auto prec = o.precision(17);
+    o << "fold_output_path = " << fold_output_path << "\n"
+      << "fold_period = " << fold_period << "\n"
+      << "fold_period_derivative = " << fold_period_derivative << "\n"
+      << "fold_nbin = " << fold_nbin << "\n"
+      << "fold_phase_offset = " << fold_phase_offset << "\n"
+      << "fold_subint_blocks = " << fold_subint_blocks << "\n";
     o.precision(prec);
   }
   return o.str();

@@ -217,6 +217,36 @@ int main(int argc, char** argv) {
   }
   const size_t fil_t = fil_mode ? cfg.filterbank_tscrunch : 1;
 
+  // pulsar folding (fold_output_path): one DM per profile
+  const bool fold_mode = !cfg.fold_output_path.empty();
+  double fold_f0 = 0.0, fold_f1 = 0.0;
+  if (fold_mode && trial_mode) {
+    SRTB_APP_LOGE("config: fold_output_path and dm_trial_list exclude each "
+                  "other (a folded profile holds one DM)");
+    return 2;
+  }
+  if (fold_mode) {
+    const double P = cfg.fold_period;
+    if (!(P > 0.0)) {
+      SRTB_APP_LOGE("config: fold_period must be positive");
+      return 2;
+    }
+    fold_f0 = 1.0 / P;
+    fold_f1 = -cfg.fold_period_derivative / (P * P);
+    if (cfg.fold_nbin < srtb_hip::kFoldMinBins ||
+        cfg.fold_nbin > srtb_hip::kFoldMaxBins) {
+      SRTB_APP_LOGE("config: fold_nbin must be in " << srtb_hip::kFoldMinBins
+                    << ".." << srtb_hip::kFoldMaxBins);
+      return 2;
+    }
+    if (!(fold_f0 * (double)(2 * cfg.spectrum_channel_count) /
+              cfg.baseband_sample_rate < 1.0)) {
+      SRTB_APP_LOGE("config: fold_period is shorter than one waterfall sample "
+                    "(2 * spectrum_channel_count / baseband_sample_rate)");
+      return 2;
+    }
+  }
+
   const size_t reserved_ref = nsamps_reserved(cfg, reserve_dm, fil_t);
   size_t reserved = reserved_ref;
   const bool udp_mode = cfg.input_file_path.empty();
@@ -273,6 +303,20 @@ int main(int argc, char** argv) {
                     << reserved << ") is not a positive multiple of 2 * "
                     << "spectrum_channel_count * filterbank_tscrunch = "
                     << per);
+      return 2;
+    }
+  }
+  if (fold_mode) {
+    ec.fold_nbin = cfg.fold_nbin;
+    ec.fold_f0 = fold_f0;
+    ec.fold_f1 = fold_f1;
+    ec.fold_phase0 = cfg.fold_phase_offset;
+    const size_t per = 2 * cfg.spectrum_channel_count;
+    if (reserved >= cfg.baseband_input_count ||
+        (cfg.baseband_input_count - reserved) % per != 0) {
+      SRTB_APP_LOGE("config: baseband_input_count - overlap ("
+                    << reserved << ") is not a positive multiple of 2 * "
+                    << "spectrum_channel_count = " << per << " (fold)");
       return 2;
     }
   }
@@ -552,6 +596,86 @@ int main(int argc, char** argv) {
                     "data stream");
   }
 
+  // pulsar folding: the engines accumulate, a sub-integration is read, written
+  // and reset between blocks (everything in flight is drained first, so the
+  // accumulators hold exactly the sub-integration's blocks)
+  std::vector<std::string> fold_stems;
+  unsigned fold_index = 0;
+  uint64_t fold_in_subint = 0, fold_first_sample = 0, fold_seen = 0;
+  uint64_t fold_first_counter = 0;
+  bool fold_drop_warned = false;
+  const bool fold_has_counter =
+      udp_mode && !PacketFormat::for_backend(fmt_name).headerless;
+  const uint64_t fold_fresh = cfg.baseband_input_count - reserved;
+  if (fold_mode) {
+    std::string stem = cfg.fold_output_path;
+    if (stem.size() > 4 && stem.compare(stem.size() - 4, 4, ".npy") == 0)
+      stem.resize(stem.size() - 4);
+    for (int si = 0; si < n_streams; ++si) {
+      std::string tag;
+      if (n_streams > 1) tag += "_s" + std::to_string(si);
+      if (comm.world() > 1) tag += "_r" + std::to_string(comm.rank());
+      fold_stems.push_back(stem + tag);
+    }
+    SRTB_APP_LOGI("fold -> " << fold_stems[0] << "_NNNN.npy (" << cfg.fold_nbin
+                             << " bins, period " << cfg.fold_period << " s, "
+                             << cfg.fold_subint_blocks
+                             << " blocks per sub-integration)");
+    if (udp_mode && n_endpoints > 1)
+      SRTB_APP_LOGW("fold: several UDP endpoints share one profile per data "
+                    "stream");
+  }
+  // index in its sample stream of the block's first sample
+  auto fold_position = [&](uint64_t counter) -> uint64_t {
+    const uint64_t ordinal = fold_seen++;
+    if (!udp_mode) {
+      // file replay: the true position, whichever blocks this rank reads
+      const uint64_t bits = (uint64_t)std::abs(cfg.baseband_input_bits);
+      return (counter - cfg.input_file_offset_bytes * 8 / bits) /
+             (uint64_t)n_streams;
+    }
+    if (!fold_has_counter) return ordinal * fold_fresh;
+    // the begin counter stamps the block's new region; the stream origin is
+    // the head of the first block
+    const auto fmt = PacketFormat::for_backend(fmt_name);
+    const uint64_t per_packet =
+        fmt.payload_size * 8 /
+        (uint64_t)std::abs(cfg.baseband_input_bits) / (uint64_t)n_streams;
+    if (ordinal == 0) fold_first_counter = counter;
+    const uint64_t n0 = (counter - fold_first_counter) * per_packet;
+    if (n0 != ordinal * fold_fresh && !fold_drop_warned) {
+      fold_drop_warned = true;
+      SRTB_APP_LOGW("fold: data was dropped before block " << counter
+                    << "; the phase follows the packet counter");
+    }
+    return n0;
+  };
+  auto fold_flush = [&] {
+    if (!fold_mode || fold_in_subint == 0) return;
+    const size_t Sf = engine.n_channels(), nb = cfg.fold_nbin;
+    std::ostringstream meta;
+    meta.precision(17);
+    meta << "f0 = " << fold_f0 << "\nf1 = " << fold_f1
+         << "\nphase0 = " << cfg.fold_phase_offset << "\nnbin = " << nb
+         << "\nfirst_sample = " << fold_first_sample
+         << "\nn_blocks = " << fold_in_subint << "\ntsamp = "
+         << 2.0 * (double)cfg.spectrum_channel_count / cfg.baseband_sample_rate
+         << "\nfreq_low = " << cfg.baseband_freq_low
+         << "\nbandwidth = " << cfg.baseband_bandwidth << "\ndm = " << cfg.dm
+         << "\nrow_order = waterfall rows: row c is the channel at "
+            "freq_low + (c + 0.5) * bandwidth / nrows\n";
+    for (int si = 0; si < n_streams; ++si) {
+      std::vector<double> acc(Sf * nb);
+      std::vector<uint64_t> hits(nb), weights(Sf);
+      engines[si]->fold_read(acc.data(), hits.data(), weights.data());
+      engines[si]->fold_reset();
+      write_fold_subint(fold_stems[si], fold_index, acc, hits, weights,
+                        meta.str());
+    }
+    ++fold_index;
+    fold_in_subint = 0;
+  };
+
   // async dump staging, lazily pinned on first detection
   std::vector<std::array<DumpStaging, 2>> staging(n_streams);
 
@@ -570,8 +694,13 @@ int main(int argc, char** argv) {
     return false;
   };
 
-  auto submit_block = [&](int bi) -> std::array<int, 2> {
+  auto submit_block = [&](int bi, uint64_t counter) -> std::array<int, 2> {
     std::array<int, 2> slots{-1, -1};
+    if (fold_mode) {
+      const uint64_t n0 = fold_position(counter);
+      if (fold_in_subint++ == 0) fold_first_sample = n0;
+      for (auto& e : engines) e->set_fold_next_sample(n0);
+    }
     if (trial_mode) {
       slots[0] = engine.submit_trials(bufs[bi], raw_bytes, trial_dms.data(),
                                       (int)trial_dms.size());
@@ -843,11 +972,17 @@ int main(int argc, char** argv) {
     BlockMsg msg;
     if (!q_in.pop(msg, stopped)) break;
     if (msg.eof) break;
-    inflight.push_back({submit_block(msg.buf_index), msg.buf_index,
-                        msg.counter});
+    if (fold_mode && cfg.fold_subint_blocks > 0 &&
+        fold_in_subint >= cfg.fold_subint_blocks) {
+      while (!inflight.empty()) drain_one();
+      fold_flush();
+    }
+    inflight.push_back({submit_block(msg.buf_index, msg.counter),
+                        msg.buf_index, msg.counter});
     if (inflight.size() >= 2) drain_one();
   }
   while (!inflight.empty()) drain_one();
+  fold_flush();
   if (held_buf >= 0) q_free.put(held_buf);
   if (write_all_fd >= 0) {
     writers.drain();  // all appends on disk before fdatasync+close

@@ -138,6 +138,51 @@ inline std::string tag_before_extension(const std::string& path,
   return path.substr(0, dot) + tag + path.substr(dot);
 }
 
+// .npy (format 1.0) of a C-ordered array: descr "<f8" or "<u8", shape
+// "(rows, cols)" or "(n,)"
+inline void write_npy_file(const std::string& path, const char* descr,
+                           const std::string& shape, const void* data,
+                           size_t nbytes) {
+  std::string header = std::string("{'descr': '") + descr +
+                       "', 'fortran_order': False, 'shape': " + shape + ", }";
+  const size_t total = 10 + header.size() + 1;
+  header += std::string((64 - total % 64) % 64, ' ');
+  header += '\n';
+  std::string head("\x93NUMPY\x01", 7);
+  head += '\0';
+  const uint16_t hlen = (uint16_t)header.size();
+  head.append(reinterpret_cast<const char*>(&hlen), 2);
+  head += header;
+  std::ofstream f(path, std::ios::binary | std::ios::trunc);
+  if (!f) throw std::runtime_error("cannot open " + path);
+  f.write(head.data(), (std::streamsize)head.size());
+  f.write(static_cast<const char*>(data), (std::streamsize)nbytes);
+}
+
+// One folded sub-integration, twin of the Python write_fold_subint:
+// {stem}_{index:04d}.npy (float64 [S][nbin], waterfall row order),
+// .hits.npy (uint64 [nbin]), .weights.npy (uint64 [S]) and .txt, whose
+// `key = value` lines the caller supplies.
+inline void write_fold_subint(const std::string& stem, unsigned index,
+                              const std::vector<double>& acc,
+                              const std::vector<uint64_t>& hits,
+                              const std::vector<uint64_t>& weights,
+                              const std::string& meta) {
+  char num[16];
+  std::snprintf(num, sizeof num, "_%04u", index);
+  const std::string base = stem + num;
+  const size_t S = weights.size(), nbin = hits.size();
+  write_npy_file(base + ".npy", "<f8",
+                 "(" + std::to_string(S) + ", " + std::to_string(nbin) + ")",
+                 acc.data(), acc.size() * sizeof(double));
+  write_npy_file(base + ".hits.npy", "<u8", "(" + std::to_string(nbin) + ",)",
+                 hits.data(), hits.size() * sizeof(uint64_t));
+  write_npy_file(base + ".weights.npy", "<u8", "(" + std::to_string(S) + ",)",
+                 weights.data(), weights.size() * sizeof(uint64_t));
+  std::ofstream f(base + ".txt", std::ios::trunc);
+  f << meta;
+}
+
 inline void write_time_series_tim(const std::string& prefix, uint64_t counter,
                                   size_t boxcar, const float* data,
                                   size_t n) {

@@ -5,6 +5,7 @@
 // this TU only adapts torch::Tensor ↔ raw pointers and streams.
 
 #include <torch/extension.h>
+#include <pybind11/numpy.h>
 #include <ATen/cuda/CUDAContext.h>
 #include <c10/cuda/CUDAGuard.h>
 
@@ -478,6 +479,60 @@ torch::Tensor t_filterbank_quantize(torch::Tensor P, torch::Tensor mean,
   return out;
 }
 
+// ---------------- pulsar folding ----------------
+
+// One fold_block() into caller-owned accumulators: acc float64 [S][nbin],
+// hits [nbin] and weights [S] as 64-bit integer tensors (the bits are u64).
+void t_fold_block(torch::Tensor wf, c10::optional<torch::Tensor> flags,
+                  int64_t valid, int64_t nbin, uint64_t phi, uint64_t dphi,
+                  torch::Tensor acc, torch::Tensor hits,
+                  torch::Tensor weights) {
+  CHECK_CUDA(wf);
+  CHECK_CONTIG(wf);
+  CHECK_CUDA(acc);
+  CHECK_CONTIG(acc);
+  CHECK_CUDA(hits);
+  CHECK_CONTIG(hits);
+  CHECK_CUDA(weights);
+  CHECK_CONTIG(weights);
+  TORCH_CHECK(wf.dim() == 2 && wf.scalar_type() == torch::kComplexFloat);
+  const int64_t S = wf.size(0), L = wf.size(1);
+  TORCH_CHECK(S >= 1 && valid >= 1 && valid <= L &&
+                  nbin >= (int64_t)kFoldMinBins &&
+                  nbin <= (int64_t)kFoldMaxBins,
+              "fold_block: bad geometry");
+  auto is_u64 = [](const torch::Tensor& t) {
+    return t.scalar_type() == torch::kInt64 ||
+           t.scalar_type() == torch::kUInt64;
+  };
+  TORCH_CHECK(acc.scalar_type() == torch::kFloat64 && acc.dim() == 2 &&
+                  acc.size(0) == S && acc.size(1) == nbin,
+              "fold_block: acc must be float64 [S][nbin]");
+  TORCH_CHECK(is_u64(hits) && hits.dim() == 1 && hits.size(0) == nbin,
+              "fold_block: hits must be 64-bit integer [nbin]");
+  TORCH_CHECK(is_u64(weights) && weights.dim() == 1 && weights.size(0) == S,
+              "fold_block: weights must be 64-bit integer [S]");
+  const uint8_t* f = nullptr;
+  if (flags.has_value()) {
+    CHECK_CUDA(*flags);
+    CHECK_CONTIG(*flags);
+    TORCH_CHECK(flags->scalar_type() == torch::kUInt8 && flags->numel() == S);
+    f = flags->data_ptr<uint8_t>();
+  }
+  auto words = torch::tensor({(int64_t)phi, (int64_t)dphi},
+                             torch::TensorOptions().dtype(torch::kInt64))
+                   .to(wf.device());
+  auto table = torch::empty({(int64_t)fold_table_words(valid)},
+                            wf.options().dtype(torch::kInt32));
+  check(fold_block(cptr(wf), f, S, L, valid, nbin,
+                   static_cast<const uint64_t*>(words.data_ptr()),
+                   static_cast<uint32_t*>(table.data_ptr()),
+                   acc.data_ptr<double>(),
+                   static_cast<uint64_t*>(hits.data_ptr()),
+                   static_cast<uint64_t*>(weights.data_ptr()), cur_stream()),
+        "fold_block");
+}
+
 // ---------------- hand-written FFT (test/bench surface) ----------------
 
 torch::Tensor t_native_fft(torch::Tensor x, int64_t sign) {
@@ -683,7 +738,8 @@ class PyEngine {
            bool enable_rfi_s1, bool enable_sk, int64_t n_slots,
            int64_t fft_backend, int64_t window_kind, bool use_hip_graph,
            int64_t max_dm_trials, int64_t fil_tscrunch, int64_t fil_fscrunch,
-           int64_t fil_nbits) {
+           int64_t fil_nbits, int64_t fold_nbin, double fold_f0,
+           double fold_f1, double fold_phase0) {
     EngineConfig c;
     c.baseband_input_count = n;
     c.baseband_input_bits = (int)nbits;
@@ -715,6 +771,11 @@ class PyEngine {
     c.fil_tscrunch = (size_t)fil_tscrunch;
     c.fil_fscrunch = (size_t)fil_fscrunch;
     c.fil_nbits = (int)fil_nbits;
+    TORCH_CHECK(fold_nbin >= 0, "fold_nbin must not be negative");
+    c.fold_nbin = (size_t)fold_nbin;
+    c.fold_f0 = fold_f0;
+    c.fold_f1 = fold_f1;
+    c.fold_phase0 = fold_phase0;
     eng_ = std::make_unique<PipelineEngine>(c, (int)n_slots);
   }
 
@@ -887,6 +948,29 @@ class PyEngine {
     return {mean.clone(), stddev.clone()};
   }
 
+  void set_fold_next_sample(uint64_t n0) { eng_->set_fold_next_sample(n0); }
+  uint64_t fold_next_sample() const { return eng_->fold_next_sample(); }
+
+  // (n0, Phi_b, dPhi_b) of the slot's last submission, Python integers
+  py::tuple fold_words(int64_t slot) {
+    const auto w = eng_->fold_words((int)slot);
+    return py::make_tuple(py::int_(w.n0), py::int_(w.phi), py::int_(w.dphi));
+  }
+
+  void fold_reset() { eng_->fold_reset(); }
+
+  // Synchronises the engine.  (acc float64 [S][nbin], hits uint64 [nbin],
+  // weights uint64 [S]) as NumPy arrays, the slots summed in slot order.
+  py::tuple fold_read() {
+    const auto S = (py::ssize_t)eng_->n_channels(),
+               nb = (py::ssize_t)eng_->fold_nbin();
+    py::array_t<double> acc({S, nb});
+    py::array_t<uint64_t> hits(nb), weights(S);
+    eng_->fold_read(acc.mutable_data(), hits.mutable_data(),
+                    weights.mutable_data());
+    return py::make_tuple(acc, hits, weights);
+  }
+
   int64_t filterbank_rows() const { return eng_->filterbank_rows(); }
   int64_t filterbank_channels() const { return eng_->filterbank_channels(); }
 
@@ -950,6 +1034,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("filterbank_channel_stats", &t_filterbank_channel_stats, py::arg("P"));
   m.def("filterbank_quantize", &t_filterbank_quantize, py::arg("P"),
         py::arg("mean"), py::arg("std"));
+  m.def("fold_block", &t_fold_block, py::arg("wf"), py::arg("flags"),
+        py::arg("valid"), py::arg("nbin"), py::arg("phi"), py::arg("dphi"),
+        py::arg("acc"), py::arg("hits"), py::arg("weights"));
   m.def("native_fft", &t_native_fft, py::arg("x"), py::arg("sign"));
   m.def("native_rfft", &t_native_rfft, py::arg("x"));
   m.def("preop_backward_fft", &t_preop_backward_fft, py::arg("spec"),
@@ -969,7 +1056,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                     double, double, double, int64_t, int64_t,
                     std::vector<std::vector<int64_t>>, bool, bool, bool,
                     int64_t, int64_t, int64_t, bool, int64_t, int64_t,
-                    int64_t, int64_t>(),
+                    int64_t, int64_t, int64_t, double, double, double>(),
            py::arg("n"), py::arg("nbits"), py::arg("channels"),
            py::arg("freq_low"), py::arg("bandwidth"), py::arg("sample_rate"),
            py::arg("dm"), py::arg("rfi_threshold") = 10.0,
@@ -981,7 +1068,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("n_slots") = 2, py::arg("fft_backend") = 2,
            py::arg("window_kind") = 0, py::arg("use_hip_graph") = false,
            py::arg("max_dm_trials") = 0, py::arg("fil_tscrunch") = 0,
-           py::arg("fil_fscrunch") = 1, py::arg("fil_nbits") = 32)
+           py::arg("fil_fscrunch") = 1, py::arg("fil_nbits") = 32,
+           py::arg("fold_nbin") = 0, py::arg("fold_f0") = 0.0,
+           py::arg("fold_f1") = 0.0, py::arg("fold_phase0") = 0.0)
       .def("submit", &PyEngine::submit, py::arg("raw"),
            py::arg("dm_override") = std::nan(""))
       .def("submit_samples", &PyEngine::submit_samples, py::arg("samples"),
@@ -1002,6 +1091,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("filterbank", &PyEngine::filterbank)
       .def("filterbank_power", &PyEngine::filterbank_power)
       .def("filterbank_stats", &PyEngine::filterbank_stats)
+      .def("set_fold_next_sample", &PyEngine::set_fold_next_sample)
+      .def("fold_next_sample", &PyEngine::fold_next_sample)
+      .def("fold_words", &PyEngine::fold_words)
+      .def("fold_reset", &PyEngine::fold_reset)
+      .def("fold_read", &PyEngine::fold_read)
       .def_property_readonly("filterbank_rows", &PyEngine::filterbank_rows)
       .def_property_readonly("filterbank_channels",
                              &PyEngine::filterbank_channels)

@@ -2,6 +2,7 @@
 
 #include <roctracer/roctx.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -12,6 +13,16 @@ namespace srtb_hip {
 
 namespace {
 constexpr double kD = 4.148808e3;  // dispersion constant (MHz^2 pc^-1 cm^3 s)
+
+// x turns, 0 <= x <= 1, as a wrapping 64-bit phase word (2^64 = one turn),
+// rounded to nearest; 1.0 wraps to 0.  From 2^53 on the scaled value is an
+// integer already, so only the range llrint can hold goes through it.
+uint64_t fold_turns_to_word(double x) {
+  const double v = std::ldexp(x, 64);
+  if (v >= 0x1p64) return 0;
+  if (v >= 0x1p63) return (uint64_t)v;
+  return (uint64_t)std::llrint(v);
+}
 
 // rocTX ranges per pipeline stage (SRTB_ROCTX=1): the rocprofv3 marker
 // domain shows unpack/fft/rfi/sk/detect spans per block — the reference's
@@ -108,6 +119,35 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
     fil_c_ = s_ / f;
   }
 
+  if (cfg.fold_nbin) {
+    if (cfg.fold_nbin < kFoldMinBins || cfg.fold_nbin > kFoldMaxBins)
+      throw std::runtime_error("fold: fold_nbin must be in " +
+                               std::to_string(kFoldMinBins) + ".." +
+                               std::to_string(kFoldMaxBins));
+    if (!(cfg.fold_f0 > 0.0) || !std::isfinite(cfg.fold_f0))
+      throw std::runtime_error("fold: fold_f0 must be positive");
+    if (!(cfg.fold_f0 * (double)(2 * s_) / cfg.sample_rate < 1.0))
+      throw std::runtime_error(
+          "fold: fold_f0 is too high, one waterfall sample (2 * channels / "
+          "sample_rate) must be shorter than a period");
+    if (!std::isfinite(cfg.fold_f1))
+      throw std::runtime_error("fold: fold_f1 must be finite");
+    if (!std::isfinite(cfg.fold_phase0))
+      throw std::runtime_error("fold: fold_phase0 must be finite");
+    if (cfg.max_dm_trials > 0)
+      throw std::runtime_error(
+          "fold: fold_nbin > 0 not together with max_dm_trials > 0 (a "
+          "profile holds one DM)");
+    if (cfg.nsamps_reserved >= n_ ||
+        (n_ - cfg.nsamps_reserved) % (2 * s_) != 0)
+      throw std::runtime_error(
+          "fold: baseband_input_count - nsamps_reserved must be a positive "
+          "multiple of 2 * channels = " + std::to_string(2 * s_) +
+          " (nsamps_reserved)");
+    fold_v_ = (n_ - cfg.nsamps_reserved) / (2 * s_);
+    fold_step_ = fold_turns_to_word(cfg.fold_f0 / cfg.sample_rate);
+  }
+
   const int np = reduce_partials();
   for (int i = 0; i < n_slots_; ++i) slots_.emplace_back(new Slot());
   for (auto& sp : slots_) {
@@ -190,6 +230,30 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
         check_hip(hipHostMalloc(&s.h_fil, cells * sizeof(float)),
                   "pinned filterbank");
       }
+    }
+    if (fold_v_) {
+      const size_t nb = cfg.fold_nbin;
+      check_hip(hipMalloc(&s.fold_acc, s_ * nb * sizeof(double)),
+                "fold acc alloc");
+      check_hip(hipMalloc(&s.fold_hits, nb * sizeof(uint64_t)),
+                "fold hits alloc");
+      check_hip(hipMalloc(&s.fold_weights, s_ * sizeof(uint64_t)),
+                "fold weights alloc");
+      check_hip(hipMalloc(&s.fold_dwords, 2 * sizeof(uint64_t)),
+                "fold words alloc");
+      check_hip(hipMalloc(&s.fold_table,
+                          fold_table_words(fold_v_) * sizeof(uint32_t)),
+                "fold table alloc");
+      check_hip(hipHostMalloc(&s.h_fold_words, 2 * sizeof(uint64_t)),
+                "pinned fold words");
+      check_hip(hipMemset(s.fold_acc, 0, s_ * nb * sizeof(double)),
+                "fold acc clear");
+      check_hip(hipMemset(s.fold_hits, 0, nb * sizeof(uint64_t)),
+                "fold hits clear");
+      check_hip(hipMemset(s.fold_weights, 0, s_ * sizeof(uint64_t)),
+                "fold weights clear");
+      // the slot's stream does not order itself after the null stream
+      check_hip(hipDeviceSynchronize(), "fold clear sync");
     }
     // backend selection (see EngineConfig::fft_backend): the forward
     // 2^29-class packed C2C always favors the native plan; the batched
@@ -325,6 +389,14 @@ PipelineEngine::~PipelineEngine() {
       if (s.h_fil_stats) (void)hipHostFree(s.h_fil_stats);
       (void)hipHostFree(s.h_fil);
     }
+    if (s.fold_acc) {
+      (void)hipFree(s.fold_acc);
+      (void)hipFree(s.fold_hits);
+      (void)hipFree(s.fold_weights);
+      (void)hipFree(s.fold_dwords);
+      (void)hipFree(s.fold_table);
+      (void)hipHostFree(s.h_fold_words);
+    }
     if (s.graph_exec) (void)hipGraphExecDestroy(s.graph_exec);
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -387,6 +459,7 @@ void PipelineEngine::enqueue_chain(Slot& s, const uint8_t* dev_raw,
   enqueue_back(s, dm, plain_row(s), /*ts_dst=*/nullptr,
                /*keep_spectrum=*/false);
   if (fil_r_) enqueue_filterbank(s);
+  if (fold_v_) enqueue_fold(s);
   s.trial_dms.clear();
   s.cur_trial = -1;
   if (record_event) {
@@ -428,6 +501,94 @@ void PipelineEngine::enqueue_filterbank(Slot& s) {
                              hipMemcpyDeviceToHost, st),
               "filterbank d2h");
   }
+}
+
+// Phase words of the block about to be submitted to the (idle) slot, from the
+// running stream position, which then advances by the block's new samples.
+// Host side of docs/ARCHITECTURE.md "Pulsar folding": fp64 plus wrapping
+// 64-bit integers; the integer product n0 * step keeps f0 * t exact over any
+// observation length.
+void PipelineEngine::stamp_fold(Slot& s) {
+  const uint64_t n0 = fold_pos_;
+  const uint64_t fresh = n_ - cfg_.nsamps_reserved;
+  const double sr = cfg_.sample_rate, f1 = cfg_.fold_f1;
+  const double t0 = (double)n0 / sr;
+  const double t_mid = (double)(n0 + fresh / 2) / sr;
+  const double p0 = cfg_.fold_phase0 - std::floor(cfg_.fold_phase0);
+  const double v0 = std::ldexp(p0, 64);  // truncated, 2^64 wraps to 0
+  const double q = 0.5 * f1 * t0 * t0;
+  const uint64_t phi = (v0 >= 0x1p64 ? 0 : (uint64_t)v0) + n0 * fold_step_ +
+                       fold_turns_to_word(q - std::floor(q));
+  const uint64_t dphi =
+      (uint64_t)(2 * s_) * fold_step_ +
+      (uint64_t)(int64_t)std::llrint(
+          std::ldexp(f1 * t_mid * ((double)(2 * s_) / sr), 64));
+  s.fold_last = FoldWords{n0, phi, dphi};
+  s.h_fold_words[0] = phi;
+  s.h_fold_words[1] = dphi;
+  fold_pos_ = n0 + fresh;
+}
+
+// Fold of the block whose back half was just enqueued: one more read of the
+// waterfall's first fold_v_ columns.  The phase words travel from the slot's
+// pinned pair to its device pair on the stream, so a captured chain replays
+// with the words of the block it is launched for.  Reads the SK flags
+// directly, like the filterbank.
+void PipelineEngine::enqueue_fold(Slot& s) {
+  check_hip(hipMemcpyAsync(s.fold_dwords, s.h_fold_words,
+                           2 * sizeof(uint64_t), hipMemcpyHostToDevice,
+                           s.stream),
+            "fold words h2d");
+  check_hip(fold_block(s.wf, cfg_.enable_sk ? s.flags : nullptr, s_, l_,
+                       fold_v_, cfg_.fold_nbin, s.fold_dwords, s.fold_table,
+                       s.fold_acc, s.fold_hits, s.fold_weights, s.stream),
+            "fold");
+}
+
+PipelineEngine::FoldWords PipelineEngine::fold_words(int slot) const {
+  if (!fold_v_) throw std::runtime_error("fold: fold_nbin = 0");
+  return slots_.at(slot)->fold_last;
+}
+
+void PipelineEngine::fold_read(double* acc, uint64_t* hits,
+                               uint64_t* weights) {
+  if (!fold_v_) throw std::runtime_error("fold: fold_nbin = 0");
+  synchronize();
+  const size_t nb = cfg_.fold_nbin, cells = s_ * nb;
+  std::vector<double> a(cells);
+  std::vector<uint64_t> h(nb), w(s_);
+  std::fill(acc, acc + cells, 0.0);
+  std::fill(hits, hits + nb, 0);
+  std::fill(weights, weights + s_, 0);
+  for (auto& sp : slots_) {  // slot order: the sum is reproducible
+    check_hip(hipMemcpy(a.data(), sp->fold_acc, cells * sizeof(double),
+                        hipMemcpyDeviceToHost),
+              "fold acc d2h");
+    check_hip(hipMemcpy(h.data(), sp->fold_hits, nb * sizeof(uint64_t),
+                        hipMemcpyDeviceToHost),
+              "fold hits d2h");
+    check_hip(hipMemcpy(w.data(), sp->fold_weights, s_ * sizeof(uint64_t),
+                        hipMemcpyDeviceToHost),
+              "fold weights d2h");
+    for (size_t i = 0; i < cells; ++i) acc[i] += a[i];
+    for (size_t i = 0; i < nb; ++i) hits[i] += h[i];
+    for (size_t i = 0; i < s_; ++i) weights[i] += w[i];
+  }
+}
+
+void PipelineEngine::fold_reset() {
+  if (!fold_v_) throw std::runtime_error("fold: fold_nbin = 0");
+  synchronize();
+  const size_t nb = cfg_.fold_nbin;
+  for (auto& sp : slots_) {
+    check_hip(hipMemset(sp->fold_acc, 0, s_ * nb * sizeof(double)),
+              "fold acc clear");
+    check_hip(hipMemset(sp->fold_hits, 0, nb * sizeof(uint64_t)),
+              "fold hits clear");
+    check_hip(hipMemset(sp->fold_weights, 0, s_ * sizeof(uint64_t)),
+              "fold weights clear");
+  }
+  check_hip(hipDeviceSynchronize(), "fold clear sync");
 }
 
 void PipelineEngine::order_after_last_chain(Slot& s, bool uses_poly) {
@@ -827,6 +988,7 @@ int PipelineEngine::submit(const void* host_bytes, size_t nbytes,
     check_hip(hipEventSynchronize(s.done), "slot wait");
     s.busy = false;
   }
+  if (fold_v_) stamp_fold(s);
   const bool graph_ok = cfg_.use_hip_graph && std::isnan(dm_override);
   if (graph_ok && s.graph_exec && s.graph_host_src == host_bytes) {
     // steady state: replay the captured chain (H2D + kernels + D2H)
@@ -878,6 +1040,7 @@ int PipelineEngine::submit_device(const void* dev_bytes, size_t nbytes,
     check_hip(hipEventSynchronize(s.done), "slot wait");
     s.busy = false;
   }
+  if (fold_v_) stamp_fold(s);
   if (wait_event)
     check_hip(hipStreamWaitEvent(s.stream, wait_event, 0), "producer wait");
   enqueue_chain(s, static_cast<const uint8_t*>(dev_bytes), nullptr,
@@ -896,6 +1059,7 @@ int PipelineEngine::submit_samples_device(const float* dev_samples,
     check_hip(hipEventSynchronize(s.done), "slot wait");
     s.busy = false;
   }
+  if (fold_v_) stamp_fold(s);
   if (wait_event)
     check_hip(hipStreamWaitEvent(s.stream, wait_event, 0), "fanout wait");
   enqueue_chain(s, nullptr, dev_samples, dm_override);

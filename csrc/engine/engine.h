@@ -9,7 +9,7 @@
 //   time series → baseline subtract → threshold counts → prefix scan →
 //   boxcar ladder (2,4,…,max) with per-length thresholds →
 //   D2H(result counters) → [filterbank: detect → stats → quantise → D2H] →
-//   event
+//   [fold: phase words H2D → turn table → counts → accumulate] → event
 //
 // Two slots, each with its own HIP stream, device buffers and hipFFT plans:
 // while slot A computes, slot B's next block uploads (the reference instead
@@ -76,6 +76,17 @@ struct EngineConfig {
   size_t fil_tscrunch = 0;
   size_t fil_fscrunch = 1;
   int fil_nbits = 32;
+  // Pulsar folding (docs/ARCHITECTURE.md): every block's waterfall is folded
+  // into per-slot fp64 [S][fold_nbin] profiles at spin frequency fold_f0 (Hz),
+  // derivative fold_f1 (Hz/s) and phase fold_phase0 (turns at stream sample
+  // 0).  fold_nbin = 0 = off, nothing is allocated; otherwise 2..65536,
+  // fold_f0 > 0 with fold_f0 * 2S / sample_rate < 1, and
+  // (N - nsamps_reserved) a multiple of 2S.  Not together with
+  // max_dm_trials > 0.
+  size_t fold_nbin = 0;
+  double fold_f0 = 0.0;
+  double fold_f1 = 0.0;
+  double fold_phase0 = 0.0;
 };
 
 constexpr int kMaxDmTrials = 256;
@@ -211,6 +222,27 @@ class PipelineEngine {
   const float* filterbank_mean_host(int slot);
   const float* filterbank_std_host(int slot);
 
+  // Pulsar folding (fold_nbin > 0; otherwise fold_read and fold_reset throw).
+  // The engine keeps a running stream position: every plain submission
+  // (submit, submit_device, submit_samples_device) folds with it as the index
+  // n0 of the block's first real sample, then advances it by
+  // N - nsamps_reserved.  set_fold_next_sample overrides it for the next
+  // submission (dropped blocks, multi-rank replay).
+  struct FoldWords {
+    uint64_t n0 = 0, phi = 0, dphi = 0;  // of a slot's last submission
+  };
+  size_t fold_nbin() const { return cfg_.fold_nbin; }
+  size_t fold_valid() const { return fold_v_; }
+  void set_fold_next_sample(uint64_t n0) { fold_pos_ = n0; }
+  uint64_t fold_next_sample() const { return fold_pos_; }
+  FoldWords fold_words(int slot) const;
+  // Synchronises the whole engine (every slot's stream), then returns the
+  // slots' accumulators summed in slot order: acc [S][nbin], hits [nbin],
+  // weights [S].  Meant for sub-integration boundaries, not for every block.
+  void fold_read(double* acc, uint64_t* hits, uint64_t* weights);
+  // Synchronises, zeroes the accumulators; the stream position stays.
+  void fold_reset();
+
  private:
   struct Slot;
   // where one backward half leaves its counters and thresholds
@@ -239,11 +271,18 @@ class PipelineEngine {
   void enqueue_trial(Slot& s, int k);
   void check_trials(int n_trials) const;
   void enqueue_filterbank(Slot& s);
+  void stamp_fold(Slot& s);
+  void enqueue_fold(Slot& s);
 
   EngineConfig cfg_;
   size_t n_, nc_, s_, l_, ts_count_, raw_bytes_;
   // filterbank geometry: valid waterfall columns, output rows and channels
   size_t fil_v_ = 0, fil_r_ = 0, fil_c_ = 0;
+  // folding: valid waterfall columns, phase step per real sample (2^64 = one
+  // turn), index in the stream of the next block's first sample
+  size_t fold_v_ = 0;
+  uint64_t fold_step_ = 0;
+  uint64_t fold_pos_ = 0;
   int n_boxcars_ = 0;
   std::vector<size_t> boxcar_lengths_;
   float sk_lo_ = 0, sk_hi_ = 0;
@@ -316,6 +355,14 @@ class PipelineEngine {
     double* fil_partials = nullptr;   // stats scratch (8-bit)
     void* h_fil = nullptr;            // pinned mirror of the output plane
     float* h_fil_stats = nullptr;     // pinned [2][C] (8-bit)
+    // folding state (allocated only with fold_nbin > 0)
+    double* fold_acc = nullptr;         // [S][nbin]
+    uint64_t* fold_hits = nullptr;      // [nbin]
+    uint64_t* fold_weights = nullptr;   // [S]
+    uint64_t* fold_dwords = nullptr;    // device {Phi_b, dPhi_b}
+    uint64_t* h_fold_words = nullptr;   // pinned source of fold_dwords
+    uint32_t* fold_table = nullptr;     // turn table scratch
+    FoldWords fold_last;
   };
   std::vector<std::unique_ptr<Slot>> slots_;
   int next_slot_ = 0;

@@ -236,6 +236,29 @@ hipError_t filterbank_quantize(const float* P, const float* mean,
                                const float* stddev, size_t R, size_t C,
                                uint8_t* out_u8, hipStream_t stream);
 
+// ---------------- pulsar folding (csrc/kernels/fold.hip) ----------------
+// Definition: docs/ARCHITECTURE.md, "Pulsar folding".
+constexpr size_t kFoldMinBins = 2;
+constexpr size_t kFoldMaxBins = 65536;
+
+// Folds the first V columns of the [S][L] waterfall at the phase words
+// words[0] = Phi, words[1] = dPhi (device memory, wrapping 64-bit fixed
+// point, 2^64 = one turn): column k has bin
+// (((Phi + k * dPhi) >> 32) * nbin) >> 32, and
+//   acc[c][b]  += sum of |wf[c][k]|^2 over the columns of bin b (fp64 [S][nbin])
+//   hits[b]    += number of columns of bin b
+//   weights[c] += V
+// where a row with flags[c] != 0 adds nothing to acc and weights; flags may
+// be null.  Every element is read, added to and written by one thread: no
+// atomics, bit-identical from run to run.  table: device scratch of
+// fold_table_words(V) 32-bit words.  1 <= V <= L, V < 2^31,
+// kFoldMinBins <= nbin <= kFoldMaxBins.
+size_t fold_table_words(size_t V);
+hipError_t fold_block(const float2* wf, const uint8_t* flags, size_t S,
+                      size_t L, size_t V, size_t nbin, const uint64_t* words,
+                      uint32_t* table, double* acc, uint64_t* hits,
+                      uint64_t* weights, hipStream_t stream);
+
 // ---------------- hand-written Stockham FFT ----------------
 // One generic pass of the LDS-staged Stockham FFT (csrc/kernels/fft.hip).
 // Index-math oracle: srtb_amd/fftref.py.  Host-side planning:

@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "csrc/kernels/display.hip",
     "csrc/kernels/fft.hip",
     "csrc/kernels/filterbank.hip",
+    "csrc/kernels/fold.hip",
     "csrc/engine/engine.cpp",
 ]
 

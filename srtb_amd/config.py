@@ -60,6 +60,12 @@ _FIELD_KINDS = {
     "filterbank_fscrunch": "int",
     "filterbank_nbits": "int",
     "filterbank_tstart_mjd": "real",
+    "fold_output_path": "str",
+    "fold_period": "real",
+    "fold_period_derivative": "real",
+    "fold_nbin": "int",
+    "fold_phase_offset": "real",
+    "fold_subint_blocks": "int",
 }
 
 
@@ -107,6 +113,15 @@ class Config:
     filterbank_fscrunch: int = 1
     filterbank_nbits: int = 8
     filterbank_tstart_mjd: float = 0.0
+    # pulsar folding: "" = off; spin period (s) and its derivative (s/s), phase
+    # bins, phase (turns) at stream sample 0, blocks per sub-integration
+    # (0 = one sub-integration for the whole run)
+    fold_output_path: str = ""
+    fold_period: float = 0.0
+    fold_period_derivative: float = 0.0
+    fold_nbin: int = 256
+    fold_phase_offset: float = 0.0
+    fold_subint_blocks: int = 0
 
     # ---- assignment from strings (expression values) ----
 
@@ -154,6 +169,14 @@ class Config:
     def dm_trials(self) -> List[float]:
         """The trial DMs of ``dm_trial_list`` ([] when the key is unset)."""
         return _parse_real_list(self.dm_trial_list)
+
+    def fold_spin(self) -> tuple:
+        """(f0 in Hz, f1 in Hz/s) of ``fold_period`` / ``fold_period_derivative``:
+        f0 = 1 / P, f1 = -Pdot / P^2."""
+        p = self.fold_period
+        if not p > 0:
+            raise ValueError("fold_period must be positive")
+        return 1.0 / p, -self.fold_period_derivative / (p * p)
 
     def copy(self) -> "Config":
         return dataclasses.replace(

@@ -320,3 +320,45 @@ def read_filterbank(path: str) -> tuple[dict, np.ndarray]:
     rows = (len(buf) - pos) // (np.dtype(dtype).itemsize * nchans)
     data = np.frombuffer(buf, dtype=dtype, offset=pos, count=rows * nchans)
     return header, data.reshape(rows, nchans).copy()
+
+
+FOLD_ROW_ORDER = ("waterfall rows: row c is the channel at "
+                  "freq_low + (c + 0.5) * bandwidth / nrows")
+
+
+def fold_subint_paths(stem: str, index: int) -> dict:
+    """File names of sub-integration ``index``: profiles, hits, weights and
+    the text sidecar."""
+    base = f"{stem}_{index:04d}"
+    return {"profile": base + ".npy", "hits": base + ".hits.npy",
+            "weights": base + ".weights.npy", "meta": base + ".txt"}
+
+
+def write_fold_subint(stem: str, index: int, acc: np.ndarray,
+                      hits: np.ndarray, weights: np.ndarray,
+                      meta: dict) -> dict:
+    """Write one folded sub-integration: float64 [S][nbin] profiles in
+    waterfall row order, uint64 hits [nbin] and weights [S], and a text
+    sidecar with one ``key = value`` per line (floats at 17 significant
+    digits).  Returns the paths."""
+    paths = fold_subint_paths(stem, index)
+    np.save(paths["profile"], np.ascontiguousarray(acc, dtype=np.float64))
+    np.save(paths["hits"], np.ascontiguousarray(hits, dtype=np.uint64))
+    np.save(paths["weights"], np.ascontiguousarray(weights, dtype=np.uint64))
+    with open(paths["meta"], "w") as f:
+        for key, value in meta.items():
+            if isinstance(value, float):
+                value = f"{value:.17g}"
+            f.write(f"{key} = {value}\n")
+    return paths
+
+
+def read_fold_meta(path: str) -> dict:
+    """The sidecar's ``key = value`` lines as a dict of strings."""
+    out = {}
+    with open(path) as f:
+        for line in f:
+            if "=" in line:
+                key, value = line.split("=", 1)
+                out[key.strip()] = value.strip()
+    return out

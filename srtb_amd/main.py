@@ -28,8 +28,8 @@ from . import ref
 from .config import Config, parse_args
 from .io import backends as bk
 from .io.file_input import FileBlockReader
-from .io.writers import (BlockProducts, FilterbankWriter,
-                         SignalWriteScheduler)
+from .io.writers import (FOLD_ROW_ORDER, BlockProducts, FilterbankWriter,
+                         SignalWriteScheduler, write_fold_subint)
 from .pipeline.cpu import CpuPipeline
 from .parallel.sharding import (DetectionAggregator, broadcast_config,
                                 init_distributed, shard_streams)
@@ -98,6 +98,108 @@ def cpu_filterbank_block(cfg: Config, wf: np.ndarray,
     return ref.filterbank_quantize(power, mean, std)
 
 
+def fold_stems(cfg: Config, n_streams: int, rank: int, world: int,
+               endpoint: int | None = None) -> list[str]:
+    """One file stem per data stream, tagged like the filterbank's files
+    (``_s{k}``, ``_r{rank}``, ``_e{i}``); a trailing ``.npy`` of
+    ``fold_output_path`` is dropped.  Sub-integration i then writes
+    ``{stem}_{i:04d}.npy``, ``.hits.npy``, ``.weights.npy`` and ``.txt``."""
+    stem = cfg.fold_output_path
+    if stem.endswith(".npy"):
+        stem = stem[:-4]
+    tag = f"_r{rank}" if world > 1 else ""
+    if endpoint is not None:
+        tag += f"_e{endpoint}"
+    return [stem + (f"_s{k}" if n_streams > 1 else "") + tag
+            for k in range(n_streams)]
+
+
+def check_fold_config(cfg: Config) -> None:
+    """Reject a fold configuration before anything is allocated."""
+    if cfg.dm_trial_list.strip():
+        raise SystemExit(
+            "config: fold_output_path and dm_trial_list exclude each other "
+            "(a folded profile holds one DM)")
+    try:
+        f0, _f1 = cfg.fold_spin()
+        ref.fold_check(cfg.spectrum_channel_count, cfg.baseband_sample_rate,
+                       f0, cfg.fold_nbin)
+    except ValueError as e:
+        raise SystemExit(f"config: {e}")
+    if cfg.fold_subint_blocks < 0:
+        raise SystemExit("config: fold_subint_blocks must not be negative")
+
+
+class FoldOutput:
+    """Sub-integration bookkeeping of one pipeline: after every
+    ``fold_subint_blocks`` blocks, and at the end of the run, the pipeline's
+    accumulators are read, written and reset."""
+
+    def __init__(self, cfg: Config, stems: list[str]):
+        self.cfg = cfg
+        self.stems = stems
+        self.index = 0
+        self.blocks = 0
+        self.first_sample = 0
+
+    def block_done(self, pipe, first_sample: int) -> None:
+        if self.blocks == 0:
+            self.first_sample = first_sample
+        self.blocks += 1
+        if self.cfg.fold_subint_blocks and \
+                self.blocks >= self.cfg.fold_subint_blocks:
+            self.flush(pipe)
+
+    def flush(self, pipe) -> None:
+        if self.blocks == 0:
+            return
+        cfg = self.cfg
+        f0, f1 = cfg.fold_spin()
+        meta = {
+            "f0": f0, "f1": f1, "phase0": float(cfg.fold_phase_offset),
+            "nbin": cfg.fold_nbin, "first_sample": self.first_sample,
+            "n_blocks": self.blocks,
+            "tsamp": 2.0 * cfg.spectrum_channel_count /
+            cfg.baseband_sample_rate,
+            "freq_low": float(cfg.baseband_freq_low),
+            "bandwidth": float(cfg.baseband_bandwidth), "dm": float(cfg.dm),
+            "row_order": FOLD_ROW_ORDER,
+        }
+        for stem, (acc, hits, weights) in zip(self.stems, pipe.fold_take()):
+            write_fold_subint(stem, self.index, acc, hits, weights, meta)
+        self.index += 1
+        self.blocks = 0
+
+
+def _cpu_folder(cfg: Config, nsamps_reserved: int):
+    if not cfg.fold_output_path:
+        return None
+    f0, f1 = cfg.fold_spin()
+    return ref.CpuFolder(cfg.baseband_input_count, nsamps_reserved,
+                         cfg.spectrum_channel_count, cfg.baseband_sample_rate,
+                         f0, f1, cfg.fold_phase_offset, cfg.fold_nbin)
+
+
+def _cpu_fold_add(folder, wf: np.ndarray) -> None:
+    """Fold the SK-zapped waterfall of one block; its all-zero rows are the
+    flagged ones."""
+    folder.add(wf, ~(wf != 0).any(axis=1))
+
+
+def _cpu_fold_take(folders) -> list:
+    out = [f.read() for f in folders]
+    for f in folders:
+        f.reset()
+    return out
+
+
+def _engine_fold_take(engines) -> list:
+    out = [e.fold_read() for e in engines]
+    for e in engines:
+        e.fold_reset()
+    return out
+
+
 def _engine_products(eng, cfg: Config, slot: int, res: dict,
                      raw: np.ndarray | None, counter: int) -> BlockProducts:
     """Build the dumpable products of one processed block from a native
@@ -127,7 +229,7 @@ class GpuStreamPipeline:
     def __init__(self, cfg: Config, nsamps_reserved: int):
         import torch
         from .ops import native
-        from .pipeline.gpu import filterbank_engine_kwargs
+        from .pipeline.gpu import filterbank_engine_kwargs, fold_engine_kwargs
         self.torch = torch
         self.C = native()
         self.cfg = cfg
@@ -147,10 +249,17 @@ class GpuStreamPipeline:
             nsamps_reserved=nsamps_reserved,
             zap_ranges=[[int(a), int(b)] for a, b in bins],
             use_phase_table=False, enable_rfi_s1=True, enable_sk=True,
-            n_slots=2, **filterbank_engine_kwargs(cfg))
+            n_slots=2, **filterbank_engine_kwargs(cfg),
+            **fold_engine_kwargs(cfg))
 
     def filterbank_blocks(self) -> list[np.ndarray]:
         return [self.eng.filterbank(self.last_slot).numpy()]
+
+    def fold_position(self, n0: int) -> None:
+        self.eng.set_fold_next_sample(n0)
+
+    def fold_take(self) -> list:
+        return _engine_fold_take([self.eng])
 
     def process_block(self, raw: np.ndarray, counter: int) -> BlockProducts:
         torch = self.torch
@@ -184,15 +293,24 @@ class GpuMultiPolPipeline:
     def __init__(self, cfg: Config, nsamps_reserved: int, fmt_name: str):
         import torch
         from .ops import native
-        from .pipeline.gpu import _make_engine, filterbank_engine_kwargs
+        from .pipeline.gpu import (_make_engine, filterbank_engine_kwargs,
+                                   fold_engine_kwargs)
         self.torch = torch
         self.C = native()
         self.cfg = cfg
         self.fmt = bk.resolve_alias(fmt_name)
         self.n_streams = bk.get_data_stream_count(fmt_name)
         self.engines = [_make_engine(self.C, cfg, nsamps_reserved, nbits=-8,
-                                     **filterbank_engine_kwargs(cfg))
+                                     **filterbank_engine_kwargs(cfg),
+                                     **fold_engine_kwargs(cfg))
                         for _ in range(self.n_streams)]
+
+    def fold_position(self, n0: int) -> None:
+        for e in self.engines:
+            e.set_fold_next_sample(n0)
+
+    def fold_take(self) -> list:
+        return _engine_fold_take(self.engines)
 
     def filterbank_blocks(self) -> list[np.ndarray]:
         return [e.filterbank(s).numpy()
@@ -261,6 +379,15 @@ class CpuMultiPolPipeline:
         self.nsamps_reserved = nsamps_reserved
         self.pipes = [CpuPipeline(cfg, nsamps_reserved)
                       for _ in range(self.n_streams)]
+        self.folders = [_cpu_folder(cfg, nsamps_reserved)
+                        for _ in range(self.n_streams)]
+
+    def fold_position(self, n0: int) -> None:
+        for f in self.folders:
+            f.next_sample = n0
+
+    def fold_take(self) -> list:
+        return _cpu_fold_take(self.folders)
 
     def filterbank_blocks(self) -> list[np.ndarray]:
         return [cpu_filterbank_block(self.cfg, r["waterfall"],
@@ -277,8 +404,11 @@ class CpuMultiPolPipeline:
         cfg = self.cfg
         out = []
         self.last_results = []
-        for pipe, samples in zip(self.pipes, self._fanout(raw)):
+        for pipe, folder, samples in zip(self.pipes, self.folders,
+                                         self._fanout(raw)):
             res = pipe.process_samples(samples)
+            if folder is not None:
+                _cpu_fold_add(folder, res["waterfall"])
             self.last_result = res
             self.last_results.append(res)
             products = BlockProducts(counter=counter, timestamp=counter,
@@ -320,6 +450,13 @@ class CpuStreamPipeline:
         self.cfg = cfg
         self.nsamps_reserved = nsamps_reserved
         self.pipe = CpuPipeline(cfg, nsamps_reserved)
+        self.folder = _cpu_folder(cfg, nsamps_reserved)
+
+    def fold_position(self, n0: int) -> None:
+        self.folder.next_sample = n0
+
+    def fold_take(self) -> list:
+        return _cpu_fold_take([self.folder])
 
     def filterbank_blocks(self) -> list[np.ndarray]:
         return [cpu_filterbank_block(self.cfg, self.last_result["waterfall"],
@@ -329,6 +466,8 @@ class CpuStreamPipeline:
         cfg = self.cfg
         res = self.pipe.process_block(raw)
         self.last_result = res
+        if self.folder is not None:
+            _cpu_fold_add(self.folder, res["waterfall"])
         products = BlockProducts(counter=counter, timestamp=counter, raw=raw)
         gate = res["zero_count"] < (cfg.signal_detect_channel_threshold *
                                     cfg.spectrum_channel_count)
@@ -397,6 +536,10 @@ def main(argv=None) -> int:
                 "config: filterbank_tscrunch must be a power of two <= 4096, "
                 "filterbank_fscrunch a power of two dividing "
                 "spectrum_channel_count, filterbank_nbits 8 or 32")
+
+    fold_on = bool(cfg.fold_output_path)
+    if fold_on:
+        check_fold_config(cfg)
 
     import importlib
     torch_spec = importlib.util.find_spec("torch")
@@ -485,6 +628,23 @@ def main(argv=None) -> int:
                 f"positive multiple of 2 * spectrum_channel_count * "
                 f"filterbank_tscrunch = {per}")
 
+    # pulsar folding: one FoldOutput per pipeline (per endpoint in UDP mode)
+    fold_outs: dict = {}
+
+    def fold_block_done(pipe, first_sample, ep=None, n_eps=1):
+        if ep not in fold_outs:
+            fold_outs[ep] = FoldOutput(cfg, fold_stems(
+                cfg, n_streams, rank, world,
+                endpoint=ep if n_eps > 1 else None))
+        fold_outs[ep].block_done(pipe, first_sample)
+
+    if fold_on:
+        valid = cfg.baseband_input_count - reserved
+        if valid <= 0 or valid % (2 * cfg.spectrum_channel_count):
+            raise SystemExit(
+                f"config: baseband_input_count - overlap = {valid} is not a "
+                f"positive multiple of 2 * spectrum_channel_count (fold)")
+
     t0 = time.time()
     n_blocks = 0
     # baseband_write_all: record every block (minus the overlap tail) into
@@ -504,9 +664,15 @@ def main(argv=None) -> int:
                                  cfg.baseband_input_bits, reserved * n_streams,
                                  cfg.input_file_offset_bytes)
         for sample_index, raw in reader:
+            if fold_on:
+                # the block's true position in its sample stream, always: a
+                # replay that skips blocks then still folds in phase
+                pipe.fold_position(sample_index // n_streams)
             for products in process(pipe, raw, sample_index):
                 writer.push(products)
             fil_append(pipe)
+            if fold_on:
+                fold_block_done(pipe, sample_index // n_streams)
             if write_all_f is not None:
                 end = raw.size - reserved_bytes if reserved_bytes else raw.size
                 write_all_f.write(raw[:end].tobytes())
@@ -561,6 +727,28 @@ def main(argv=None) -> int:
             finally:
                 provider.close()
 
+        # fold position of a UDP block: from its begin counter where the
+        # packet format carries one, else from the block ordinal
+        payload = backend.packet_payload_size - backend.packet_header_size
+        per_packet = (payload * 8 // bits // n_streams
+                      if backend.packet_header_size else 0)
+        fold_first: dict = {}
+        fold_seen: dict = {}
+        fold_warned: set = set()
+
+        def udp_fold_position(ep, ts):
+            k = fold_seen.get(ep, 0)
+            fold_seen[ep] = k + 1
+            if not per_packet:
+                return k * cfg.baseband_input_count
+            first = fold_first.setdefault(ep, ts)
+            n0 = (ts - first) * per_packet
+            if n0 != k * cfg.baseband_input_count and ep not in fold_warned:
+                fold_warned.add(ep)
+                print(f"[srtb_amd] fold: endpoint {ep} dropped data before "
+                      f"block {ts}; the phase follows the packet counter")
+            return n0
+
         threads = [threading.Thread(target=receiver, args=(ep,), daemon=True)
                    for ep in my]
         for t in threads:
@@ -570,9 +758,14 @@ def main(argv=None) -> int:
                 ep, blk, ts = q.get(timeout=0.2)
             except _queue.Empty:
                 continue
+            if fold_on:
+                n0 = udp_fold_position(ep, ts)
+                pipes[ep].fold_position(n0)
             for products in process(pipes[ep], blk, ts):
                 writer.push(products)
             fil_append(pipes[ep], ep, len(my))
+            if fold_on:
+                fold_block_done(pipes[ep], n0, ep, len(my))
             state["n"] += 1
             gui_update(pipes[ep], state["n"], len(writer.written))
         state["stop"] = True
@@ -583,6 +776,8 @@ def main(argv=None) -> int:
     for ws in fil_writers.values():
         for w in ws:
             w.close()
+    for ep, out in fold_outs.items():
+        out.flush(pipe if cfg.input_file_path else pipes[ep])
     elapsed = time.time() - t0
     if gui is not None:
         # keep serving the last frames briefly (the reference GUI keeps its

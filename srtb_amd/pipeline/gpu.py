@@ -31,6 +31,16 @@ def filterbank_engine_kwargs(cfg: Config) -> dict:
             "fil_nbits": cfg.filterbank_nbits}
 
 
+def fold_engine_kwargs(cfg: Config) -> dict:
+    """Engine keywords that switch pulsar folding on ({} while
+    ``fold_output_path`` is unset)."""
+    if not cfg.fold_output_path:
+        return {}
+    f0, f1 = cfg.fold_spin()
+    return {"fold_nbin": cfg.fold_nbin, "fold_f0": f0, "fold_f1": f1,
+            "fold_phase0": cfg.fold_phase_offset}
+
+
 def _make_engine(C, cfg: Config, nsamps_reserved: int, nbits: int,
                  n: int | None = None, n_slots: int = 2,
                  max_dm_trials: int = 0, **engine_kwargs):

@@ -14,6 +14,8 @@ NumPy's ``ifft`` is multiplied back by ``n``.
 
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 # Dispersion constant, MHz^2 pc^-1 cm^3 s
@@ -491,6 +493,132 @@ def filterbank_header_fields(freq_low: float, bandwidth: float,
         "nchans": C,
         "tsamp": 2.0 * spectrum_channel_count * tscrunch / sample_rate,
     }
+
+
+# ---------------------------------------------------------------------------
+# Pulsar folding (no reference counterpart; definition in
+# docs/ARCHITECTURE.md, "Pulsar folding").  Phase is a wrapping 64-bit word,
+# 2^64 = one turn; everything here is in Python integers and float64.
+# ---------------------------------------------------------------------------
+
+_TURN = 1 << 64
+_WORD = _TURN - 1
+
+
+def _turns_to_word(x: float) -> int:
+    """x turns (0 <= x <= 1) as a phase word, rounded to nearest, 1 -> 0."""
+    return round(math.ldexp(x, 64)) & _WORD
+
+
+def fold_phase_step(sample_rate: float, f0: float) -> int:
+    """Phase step per real sample: llrint(f0 / sample_rate * 2^64)."""
+    return round(math.ldexp(f0 / sample_rate, 64))
+
+
+def fold_check(spectrum_channel_count: int, sample_rate: float, f0: float,
+               nbin: int) -> None:
+    """The rejections shared by every layer."""
+    if not 2 <= nbin <= 65536:
+        raise ValueError("fold_nbin must be in 2..65536")
+    if not f0 > 0 or not math.isfinite(f0):
+        raise ValueError("fold_f0 (1 / fold_period) must be positive")
+    if not f0 * (2 * spectrum_channel_count) / sample_rate < 1.0:
+        raise ValueError("fold_f0 is too high: one waterfall sample "
+                         "(2 * channels / sample_rate) must be shorter than "
+                         "a period")
+
+
+def fold_phase_words(n0: int, N: int, nsamps_reserved: int, S: int,
+                     sample_rate: float, f0: float, f1: float,
+                     phase0: float) -> tuple[int, int]:
+    """(Phi_b, dPhi_b) of the block whose first real sample has index ``n0``
+    in the stream: the phase word of waterfall column 0 and the step per
+    column, at spin frequency f0 (Hz), derivative f1 (Hz/s) and phase0 turns
+    at stream sample 0.  f0 * t is the integer product n0 * step, exact over
+    any observation length; only the f1 terms go through float64."""
+    step = fold_phase_step(sample_rate, f0)
+    fresh = N - nsamps_reserved
+    t0 = float(n0) / sample_rate
+    t_mid = float(n0 + fresh // 2) / sample_rate
+    p0 = phase0 - math.floor(phase0)
+    q = 0.5 * f1 * t0 * t0
+    phi = ((int(math.ldexp(p0, 64)) & _WORD) + n0 * step
+           + _turns_to_word(q - math.floor(q))) & _WORD
+    dphi = (2 * S * step
+            + round(math.ldexp(f1 * t_mid * (float(2 * S) / sample_rate), 64))
+            ) & _WORD
+    return phi, dphi
+
+
+def fold_bins(phi: int, dphi: int, V: int, nbin: int) -> np.ndarray:
+    """bin(k) = (((phi + k * dphi) mod 2^64 >> 32) * nbin) >> 32, k < V."""
+    return np.array([((((phi + k * dphi) & _WORD) >> 32) * nbin) >> 32
+                     for k in range(V)], dtype=np.int64)
+
+
+def fold_block(wf: np.ndarray, V: int, bins: np.ndarray, nbin: int,
+               flags: np.ndarray | None = None
+               ) -> tuple[np.ndarray, np.ndarray]:
+    """(fold float64 [S][nbin], hits uint64 [nbin]) of one [S][L] waterfall:
+    fold[c][b] = sum of |wf[c][k]|^2 over the k < V with bins[k] = b, rows
+    with flags[c] != 0 contribute 0; hits[b] = number of such k."""
+    wf = np.asarray(wf)
+    S, L = wf.shape
+    if not 0 < V <= L or len(bins) != V:
+        raise ValueError("fold_block: bad geometry")
+    p = (wf.real[:, :V].astype(np.float64) ** 2
+         + wf.imag[:, :V].astype(np.float64) ** 2)
+    if flags is not None:
+        p[np.asarray(flags).astype(bool)] = 0.0
+    fold = np.zeros((S, nbin), dtype=np.float64)
+    np.add.at(fold.T, bins, p.T)
+    hits = np.bincount(bins, minlength=nbin).astype(np.uint64)
+    return fold, hits
+
+
+class CpuFolder:
+    """Accumulates blocks the way the engine does: a running stream position
+    that advances by N - nsamps_reserved per block, fp64 profiles, u64 hits
+    and weights."""
+
+    def __init__(self, N: int, nsamps_reserved: int, S: int,
+                 sample_rate: float, f0: float, f1: float, phase0: float,
+                 nbin: int):
+        fold_check(S, sample_rate, f0, nbin)
+        if nsamps_reserved >= N or (N - nsamps_reserved) % (2 * S) != 0:
+            raise ValueError("fold: baseband_input_count - nsamps_reserved "
+                             "must be a positive multiple of 2 * channels")
+        self.N, self.reserved, self.S = N, nsamps_reserved, S
+        self.sample_rate, self.f0, self.f1 = sample_rate, f0, f1
+        self.phase0, self.nbin = phase0, nbin
+        self.V = (N - nsamps_reserved) // (2 * S)
+        self.next_sample = 0
+        self.reset()
+
+    def reset(self) -> None:
+        self.acc = np.zeros((self.S, self.nbin), dtype=np.float64)
+        self.hits = np.zeros(self.nbin, dtype=np.uint64)
+        self.weights = np.zeros(self.S, dtype=np.uint64)
+
+    def add(self, wf: np.ndarray, flags: np.ndarray | None = None
+            ) -> tuple[int, int, int]:
+        """Fold one block at the running position; returns (n0, phi, dphi)."""
+        n0 = self.next_sample
+        phi, dphi = fold_phase_words(n0, self.N, self.reserved, self.S,
+                                     self.sample_rate, self.f0, self.f1,
+                                     self.phase0)
+        bins = fold_bins(phi, dphi, self.V, self.nbin)
+        fold, hits = fold_block(wf, self.V, bins, self.nbin, flags)
+        self.acc += fold
+        self.hits += hits
+        good = (np.ones(self.S, dtype=bool) if flags is None
+                else ~np.asarray(flags).astype(bool))
+        self.weights += np.where(good, self.V, 0).astype(np.uint64)
+        self.next_sample = n0 + self.N - self.reserved
+        return n0, phi, dphi
+
+    def read(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        return self.acc.copy(), self.hits.copy(), self.weights.copy()
 
 
 # ---------------------------------------------------------------------------
