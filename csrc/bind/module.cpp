@@ -339,6 +339,34 @@ torch::Tensor t_inclusive_scan(torch::Tensor ts) {
   return out;
 }
 
+// (thresholds float32 [n], counts int32 [n]) of the fused boxcar ladder
+std::vector<torch::Tensor> t_boxcar_ladder(torch::Tensor cumsum,
+                                           std::vector<int64_t> lengths,
+                                           double snr) {
+  CHECK_CUDA(cumsum);
+  CHECK_CONTIG(cumsum);
+  TORCH_CHECK(cumsum.scalar_type() == torch::kFloat32);
+  TORCH_CHECK(!lengths.empty() && lengths.size() <= 12,
+              "1 to 12 boxcar lengths");
+  std::vector<size_t> ls;
+  for (int64_t L : lengths) {
+    TORCH_CHECK(L > 0, "boxcar lengths must be positive");
+    ls.push_back((size_t)L);
+  }
+  const int64_t nl = (int64_t)ls.size();
+  auto partials = torch::empty({nl * 2 * reduce_partials()},
+                               cumsum.options().dtype(torch::kFloat64));
+  auto thr = torch::empty({nl}, cumsum.options());
+  auto counts = torch::zeros({nl}, cumsum.options().dtype(torch::kInt32));
+  check(boxcar_ladder(cumsum.data_ptr<float>(), cumsum.numel(), ls.data(),
+                      (int)nl, partials.data_ptr<double>(), (float)snr,
+                      thr.data_ptr<float>(),
+                      reinterpret_cast<unsigned*>(counts.data_ptr<int32_t>()),
+                      cur_stream()),
+        "boxcar_ladder");
+  return {thr, counts};
+}
+
 torch::Tensor t_boxcar(torch::Tensor cumsum, int64_t L) {
   CHECK_CUDA(cumsum);
   const int64_t n_out = cumsum.numel() - L;
@@ -553,6 +581,40 @@ torch::Tensor t_native_fft(torch::Tensor x, int64_t sign) {
   }
   check(hipStreamSynchronize(stream), "native_fft sync");  // plan is local
   return out;
+}
+
+// Batched backward NativeFft of a [rows][len] tensor with the spectral-
+// kurtosis sums accumulated in the final DIF pass's store, as the engine's
+// waterfall transform runs it: (out, s2s4 float32 [rows][2]).
+std::vector<torch::Tensor> t_native_fft_sk(torch::Tensor x) {
+  CHECK_CUDA(x);
+  CHECK_CONTIG(x);
+  TORCH_CHECK(x.scalar_type() == torch::kComplexFloat && x.dim() == 2);
+  const size_t rows = x.size(0), len = x.size(1);
+  auto stream = cur_stream();
+  NativeFft plan;
+  plan.plan(len, rows, +1, stream);
+  const int wpr = plan.dif_sk_wgs_per_row();
+  TORCH_CHECK(wpr > 0, "native_fft_sk: the plan for length ", len,
+              " has no fused spectral-kurtosis epilogue");
+  auto partials = torch::empty({(int64_t)rows * wpr, 2},
+                               x.options().dtype(torch::kFloat32));
+  auto s2s4 = torch::empty({(int64_t)rows, 2},
+                           x.options().dtype(torch::kFloat32));
+  auto out = torch::empty_like(x);
+  auto* pp = reinterpret_cast<float2*>(partials.data_ptr<float>());
+  if (plan.n_passes() == 1) {
+    plan.exec(cptr(x), cptr(out), stream, nullptr, pp);
+  } else {
+    auto work = x.clone();  // passes 0..k-2 run in place on the input copy
+    plan.exec(cptr(work), cptr(out), stream, nullptr, pp);
+  }
+  check(sk_combine_partials(pp, rows, wpr,
+                            reinterpret_cast<float2*>(s2s4.data_ptr<float>()),
+                            stream),
+        "sk_combine_partials");
+  check(hipStreamSynchronize(stream), "native_fft_sk sync");  // plan is local
+  return {out, s2s4};
 }
 
 // Batched backward NativeFft with the fused RFI + zap + dedispersion pre-op
@@ -890,12 +952,51 @@ class PyEngine {
 
   void synchronize() { eng_->synchronize(); }
 
-  torch::Tensor waterfall(int64_t slot) {
+  // zap = false (test surface): a COPY of the waterfall as the chain left
+  // it, without triggering the deferred spectral-kurtosis row zap
+  torch::Tensor waterfall(int64_t slot, bool zap) {
     const auto S = (int64_t)eng_->n_channels(), L = (int64_t)eng_->waterfall_len();
-    return torch::from_blob(eng_->waterfall_ptr((int)slot), {S, L},
+    const auto opt = torch::TensorOptions()
+                         .dtype(torch::kComplexFloat)
+                         .device(torch::kCUDA);
+    if (!zap) {
+      sync_slot(slot);
+      return torch::from_blob(
+                 const_cast<float2*>(eng_->waterfall_unzapped_ptr((int)slot)),
+                 {S, L}, opt)
+          .clone();
+    }
+    return torch::from_blob(eng_->waterfall_ptr((int)slot), {S, L}, opt);
+  }
+
+  void sync_slot(int64_t slot) {
+    check(hipStreamSynchronize(eng_->stream((int)slot)), "slot sync");
+  }
+
+  // [S][2] float32 copy of the slot's <sum|x|^2, sum|x|^4> (test surface)
+  torch::Tensor sk_stats(int64_t slot) {
+    const float2* p = eng_->sk_stats_ptr((int)slot);
+    TORCH_CHECK(p, "sk_stats: the engine was built with enable_sk = false");
+    sync_slot(slot);
+    return torch::from_blob(const_cast<float2*>(p),
+                            {(int64_t)eng_->n_channels(), 2},
                             torch::TensorOptions()
-                                .dtype(torch::kComplexFloat)
-                                .device(torch::kCUDA));
+                                .dtype(torch::kFloat32)
+                                .device(torch::kCUDA))
+        .clone();
+  }
+
+  // [S] uint8 copy of the slot's spectral-kurtosis flags (test surface)
+  torch::Tensor sk_flags(int64_t slot) {
+    const uint8_t* p = eng_->sk_flags_ptr((int)slot);
+    TORCH_CHECK(p, "sk_flags: the engine was built with enable_sk = false");
+    sync_slot(slot);
+    return torch::from_blob(const_cast<uint8_t*>(p),
+                            {(int64_t)eng_->n_channels()},
+                            torch::TensorOptions()
+                                .dtype(torch::kUInt8)
+                                .device(torch::kCUDA))
+        .clone();
   }
 
   torch::Tensor time_series(int64_t slot) {
@@ -1023,6 +1124,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("count_signal", &t_count_signal);
   m.def("inclusive_scan", &t_inclusive_scan);
   m.def("boxcar", &t_boxcar);
+  m.def("boxcar_ladder", &t_boxcar_ladder, py::arg("cumsum"),
+        py::arg("lengths"), py::arg("snr"));
   m.def("resample_power", &t_resample_power);
   m.def("normalize_by_mean", &t_normalize_by_mean);
   m.def("generate_pixmap", &t_generate_pixmap);
@@ -1038,6 +1141,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("valid"), py::arg("nbin"), py::arg("phi"), py::arg("dphi"),
         py::arg("acc"), py::arg("hits"), py::arg("weights"));
   m.def("native_fft", &t_native_fft, py::arg("x"), py::arg("sign"));
+  m.def("native_fft_sk", &t_native_fft_sk, py::arg("x"));
   m.def("native_rfft", &t_native_rfft, py::arg("x"));
   m.def("preop_backward_fft", &t_preop_backward_fft, py::arg("spec"),
         py::arg("maxcol_log2"), py::arg("final_log2"), py::arg("f_min"),
@@ -1085,7 +1189,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("dm_time_plane", &PyEngine::dm_time_plane)
       .def("cumsum", &PyEngine::cumsum)
       .def("synchronize", &PyEngine::synchronize)
-      .def("waterfall", &PyEngine::waterfall)
+      .def("waterfall", &PyEngine::waterfall, py::arg("slot"),
+           py::arg("zap") = true)
+      .def("sk_stats", &PyEngine::sk_stats)
+      .def("sk_flags", &PyEngine::sk_flags)
       .def("time_series", &PyEngine::time_series)
       .def("boxcar_series", &PyEngine::boxcar_series)
       .def("filterbank", &PyEngine::filterbank)

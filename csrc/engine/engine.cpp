@@ -281,8 +281,12 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
                       /*final_log2=*/8);
         else
           s.nbwd.plan(l_, s_, +1, s.stream);
+        // the fused SK sums are those of the transform's own output: with a
+        // non-rectangular window the waterfall is de-applied afterwards, so
+        // the sums come from sk_row_stats on the de-applied rows instead and
+        // the partials do not exist (enqueue_back keys on the pointer)
         const int wpr = s.nbwd.dif_sk_wgs_per_row();
-        if (cfg.enable_sk && wpr > 0)
+        if (cfg.enable_sk && wpr > 0 && cfg.window_kind == 0)
           check_hip(hipMalloc(&s.sk_dif_partials,
                               s_ * (size_t)wpr * sizeof(float2)),
                     "sk dif partials");
@@ -705,8 +709,7 @@ void PipelineEngine::enqueue_back(Slot& s, double dm, const ResultRow& row,
   float2* wf;
   if (keep_spectrum && fuse_into_bwd) {
     s.nbwd.exec(s.spec, reinterpret_cast<float2*>(s.samples), st, &pre,
-                watfft_window_ ? nullptr : s.sk_dif_partials, nullptr, 2,
-                /*first_pass_out=*/s.trial_w);
+                s.sk_dif_partials, nullptr, 2, /*first_pass_out=*/s.trial_w);
     wf = reinterpret_cast<float2*>(s.samples);
   } else if (keep_spectrum) {
     check_hip(rfi_dedisperse_fused(
@@ -724,8 +727,7 @@ void PipelineEngine::enqueue_back(Slot& s, double dm, const ResultRow& row,
     }
   } else if (fuse_into_bwd) {
     s.nbwd.exec(s.spec, reinterpret_cast<float2*>(s.samples), st, &pre,
-                watfft_window_ ? nullptr : s.sk_dif_partials, nullptr, 2,
-                fr2c ? s.xbuf : nullptr);
+                s.sk_dif_partials, nullptr, 2, fr2c ? s.xbuf : nullptr);
     wf = reinterpret_cast<float2*>(s.samples);
   } else {
     check_hip(rfi_dedisperse_fused(
@@ -753,7 +755,9 @@ void PipelineEngine::enqueue_back(Slot& s, double dm, const ResultRow& row,
   const uint8_t* ts_flags = nullptr;
   if (cfg_.enable_sk) {
     // 6. spectral kurtosis: row stats (fused into the backward DIF store
-    //    when available — saves the 4 GB re-read) → flags → zap rows
+    //    when available — saves the 4 GB re-read) → flags → zap rows.
+    //    sk_dif_partials exists only where the exec above was given it and
+    //    its sums are those of the final waterfall (no window de-apply).
     if (fuse_into_bwd && s.sk_dif_partials)
       check_hip(sk_combine_partials(s.sk_dif_partials, s_,
                                     s.nbwd.dif_sk_wgs_per_row(), s.s2s4, st),
@@ -1101,6 +1105,16 @@ float2* PipelineEngine::waterfall_ptr(int slot) {
     s.wf_zap_pending = false;
   }
   return wf;
+}
+const float2* PipelineEngine::waterfall_unzapped_ptr(int slot) const {
+  const Slot& s = *slots_.at(slot);
+  return s.wf ? s.wf : s.spec;
+}
+const float2* PipelineEngine::sk_stats_ptr(int slot) const {
+  return cfg_.enable_sk ? slots_.at(slot)->s2s4 : nullptr;
+}
+const uint8_t* PipelineEngine::sk_flags_ptr(int slot) const {
+  return cfg_.enable_sk ? slots_.at(slot)->flags : nullptr;
 }
 float* PipelineEngine::time_series_ptr(int slot) { return slots_.at(slot)->ts; }
 float* PipelineEngine::cumsum_ptr(int slot) { return slots_.at(slot)->cumsum; }

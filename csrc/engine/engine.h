@@ -197,6 +197,12 @@ class PipelineEngine {
   // Device pointers of a slot (valid after wait(slot)) — for tests, dumps and
   // the display path.
   float2* waterfall_ptr(int slot);   // [S][L]
+  // Test surface: the waterfall as the chain left it (waterfall_ptr without
+  // the deferred row zap) and the spectral-kurtosis products of the slot's
+  // last back half; sk_* are null with enable_sk = false.
+  const float2* waterfall_unzapped_ptr(int slot) const;
+  const float2* sk_stats_ptr(int slot) const;  // [S] <sum|x|^2, sum|x|^4>
+  const uint8_t* sk_flags_ptr(int slot) const;  // [S]
   float* time_series_ptr(int slot);  // [ts_count]
   float* cumsum_ptr(int slot);       // [ts_count]
   // Recompute one boxcar series into the slot's boxcar buffer and return it

@@ -181,6 +181,9 @@ hipError_t inclusive_scan(const float* in, float* out, size_t n,
 // launches, derived directly from the cumulative sum (no box arrays).
 // partials: device scratch of n_lengths * 2 * reduce_partials() doubles;
 // out_thr/out_counts: [n_lengths] each (counts must be zeroed beforehand).
+// A length >= ts_count has no window: its count stays 0 and its threshold
+// carries no meaning (0, or NaN for a length equal to ts_count); the engine
+// never builds such a ladder.
 hipError_t boxcar_ladder(const float* cumsum, size_t ts_count,
                          const size_t* lengths, int n_lengths,
                          double* partials, float snr, float* out_thr,

@@ -97,11 +97,13 @@ namespace {
 // inter-pass twiddle e^{i * m * tw_angle}: exact integer reduction (m < M),
 // fp64 angle, fast f32 sincos — table gathers spread over up to 64 cache
 // lines per wave instruction and were the column kernel's bottleneck.
+// The hardware sine and cosine take their argument in revolutions: m / M is
+// handed over as such (exact in float up to M = 2^24) instead of rounding an
+// angle of up to 2 pi to float and scaling it back by 1 / (2 pi), which cost
+// up to 7 ulp of phase per twiddle and one more multiplication.
 __device__ inline float2 tw_eval(unsigned long long m, double angle) {
-  const float th = (float)((double)m * angle);
-  float s, c;
-  __sincosf(th, &s, &c);
-  return make_float2(c, s);
+  const float r = (float)((double)m * (angle * 0.15915494309189535));
+  return make_float2(__builtin_amdgcn_cosf(r), __builtin_amdgcn_sinf(r));
 }
 
 __device__ inline void digits(unsigned long long id, const FftPassDescDev& d,
@@ -1039,13 +1041,18 @@ __global__ void __launch_bounds__(256)
   constexpr int N = 64 * E;
   constexpr int EL2 = col_ilog2(E);
   extern __shared__ float2 lds[];
-  // layout: [ltw: N][w64: 64][per-wave transpose buffers: 4 * 64*(E+1)];
+  // layout: [ltw: N][w64: 64][anc: NA][per-wave transpose buffers:
+  // 4 * 64*(E+1)], anc[a][lane] = W_N^(lane * 8 (a+1)) the restart points of
+  // step 2's twiddle recurrence (NA = 64 * (E/8 - 1) entries, none below
+  // E = 16);
   // GT = twiddles read from GLOBAL (L2-hot) — frees N+64 float2 of LDS
   // for one more workgroup per CU
   const int wave = (int)(threadIdx.x >> 6);
   const int lane = (int)(threadIdx.x & 63);
   const float2* ltw;
   const float2* w64;
+  [[maybe_unused]] const float2* anc = nullptr;
+  constexpr int NA = E >= 16 ? 64 * (E / 8 - 1) : 0;
   float2* buf;
   if constexpr (GT) {
     ltw = tw_n;
@@ -1057,10 +1064,14 @@ __global__ void __launch_bounds__(256)
     for (int j = (int)threadIdx.x; j < N; j += (int)blockDim.x)
       ltw_l[j] = tw_n[j];
     if (threadIdx.x < 64) w64_l[threadIdx.x] = tw_n[(size_t)threadIdx.x * E];
+    float2* anc_l = w64_l + 64;
+    for (int j = (int)threadIdx.x; j < NA; j += (int)blockDim.x)
+      anc_l[j] = tw_n[((j & 63) * 8 * ((j >> 6) + 1)) & (N - 1)];
     __syncthreads();  // tables only; the data path below is wave-local
     ltw = ltw_l;
     w64 = w64_l;
-    buf = w64_l + 64 + (size_t)wave * 64 * (E + 1);
+    anc = anc_l;
+    buf = anc_l + NA + (size_t)wave * 64 * (E + 1);
   }
 
   const unsigned rev = (__brev((unsigned)lane) >> 26);  // bitrev6(lane)
@@ -1092,13 +1103,27 @@ __global__ void __launch_bounds__(256)
     }
     // step 2: twiddle W_N^(lane*k2) by recurrence from W_N^lane — the
     // direct gather ltw[lane*k2] is a stride-k2 LDS access (up to 8-way
-    // bank conflicts at even k2); one stride-1 gather + E-2 register
-    // cmuls is conflict-free (phase error ~E ulp, within fp32 FFT noise)
+    // bank conflicts at even k2); one stride-1 gather + register cmuls is
+    // conflict-free.  The recurrence multiplies wbase's rounding error by
+    // k2, so it restarts every 8 steps from anc[k2/8 - 1][lane], a stride-1
+    // read as well: the phase error stays at the ~8 ulp of E = 8 (measured
+    // per element against fp64, an unbroken chain gave 3x rocFFT's error at
+    // E = 32; restarting from ltw[lane*k2] itself, a 16-way bank conflict,
+    // cost 20 % of the kernel's time there).  Measured on 2^27 elements,
+    // ms before -> after: 512 and 1024 unchanged (0.51, 0.53); 2048 forward
+    // 1.27 -> 1.29, backward 1.26 -> 1.50.  The backward figure did not move
+    // when the restart values were read once per wave into registers
+    // instead (forward then 1.61): at 256 VGPRs the E = 32 instance is at
+    // the mercy of the scheduler, and the engine's automatic backend takes
+    // rocFFT for a waterfall this short.
     {
       const float2 wbase = ltw[lane];
       float2 w = wbase;
 #pragma unroll
       for (int k2 = 1; k2 < E; ++k2) {
+        if ((k2 & 7) == 0)
+          w = GT ? tw_n[(lane * k2) & (N - 1)]
+                 : anc[((k2 >> 3) - 1) * 64 + lane];
         v[k2] = cmulf(v[k2], w);
         w = cmulf(w, wbase);
       }
@@ -1796,7 +1821,8 @@ hipError_t fft_wave_pass(const float2* in, float2* out, uint32_t n,
   }();
   const size_t lds_bytes =
       (gt ? 4ull * 64 * (E + 1)
-          : (size_t)n + 64 + 4ull * 64 * (E + 1)) * sizeof(float2);
+          : (size_t)n + 64 + (E >= 16 ? 64ull * (E / 8 - 1) : 0) +
+                4ull * 64 * (E + 1)) * sizeof(float2);
   // enough waves to fill the chip ~8x; each wave strides over FFTs
   uint32_t grid = (uint32_t)((n_ffts + 3) / 4);
   if (grid > 16384) grid = 16384;

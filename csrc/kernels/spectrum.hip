@@ -912,7 +912,10 @@ hipError_t time_series_2stage(const float2* wf, const uint8_t* flags,
     return time_series(wf, flags, rows, len, ts_count, ts, stream);
   int chunks = time_series_chunks(ts_count);
   if ((size_t)chunks > rows) chunks = (int)rows;
-  const uint32_t gx = (uint32_t)((ts_count / 2 + kBlock - 1) / kBlock);
+  // one thread per column pair, the unpaired last column of an odd ts_count
+  // included (ts_count / 2 threads left it out whenever that was a multiple
+  // of the block size, e.g. ts_count = 4097)
+  const uint32_t gx = (uint32_t)(((ts_count + 1) / 2 + kBlock - 1) / kBlock);
   dim3 grid(gx, (uint32_t)chunks);
   if (flags)
     hipLaunchKernelGGL((k_time_series_partial<true>), grid, dim3(kBlock), 0,

@@ -90,7 +90,7 @@ def test_fft_forced_column_widths(C, maxcol, monkeypatch):
     default factorization otherwise leaves N=64 (used by the 2^30 bench
     path) and small widths untested."""
     monkeypatch.setenv("SRTB_FFT_MAXCOL", maxcol)
-    n = 1 << 20  # rest 12 bits over the 256 final
+    n = 1 << 20  # rest 14 bits over the 64 final
     x = rand_c64((2, n), seed=int(maxcol))
     xt = torch.from_numpy(x).cuda()
     out = C.native_fft(xt, -1).cpu().numpy()

@@ -262,6 +262,178 @@ def test_boxcar(C):
     np.testing.assert_allclose(box, expect, rtol=1e-3, atol=2e-2)
 
 
+# ---------------- detection and SK, exact ----------------
+#
+# Inputs are small integers, so every float32 partial sum is an integer
+# below 2^24 and exact in any order: the kernels must reproduce the float64
+# sums bit for bit.
+
+U = 2.0 ** -24
+
+
+def int_waterfall(rows, length, amp, seed):
+    rng = np.random.default_rng(seed)
+    re = rng.integers(-amp, amp + 1, size=(rows, length))
+    im = rng.integers(-amp, amp + 1, size=(rows, length))
+    return (re + 1j * im).astype(np.complex64)
+
+
+def ts_flag_pattern(kind, rows):
+    """none; one whole chunk of the two-stage kernel (its second: rows
+    [per, 2 per) with per = ceil(rows / min(64, rows))) plus the last row;
+    every third row; all rows."""
+    f = np.zeros(rows, dtype=np.uint8)
+    if kind == "chunk":
+        per = -(-rows // min(64, rows))
+        f[per:2 * per] = 1
+        f[-1] = 1
+    elif kind == "third":
+        f[::3] = 1
+    elif kind == "all":
+        f[:] = 1
+    return None if kind == "none" else f
+
+
+@pytest.mark.parametrize("flags", ["none", "chunk", "third", "all"])
+@pytest.mark.parametrize("rows,length,ts_count", [
+    (16, 256, 200),
+    (70, 514, 511),      # odd ts_count: the last column has no pair;
+                         # 70 rows over 64 chunks: the last chunks are empty
+    (3, 8, 7),           # fewer rows than chunks
+    (130, 4098, 4097),   # 9 column blocks, 3 rows per chunk, 130 = 43 * 3 + 1
+    (5, 255, 255),       # odd row length: the single-pass fallback
+])
+def test_time_series_exact(C, rows, length, ts_count, flags):
+    wf = int_waterfall(rows, length, 15, seed=rows + length)
+    f = ts_flag_pattern(flags, rows)
+    p = wf.real.astype(np.float64) ** 2 + wf.imag.astype(np.float64) ** 2
+    if f is not None:
+        p[f != 0] = 0
+    want = p[:, :ts_count].sum(axis=0)
+    assert want.max() < 2 ** 24
+    got = C.time_series(to_gpu(wf), None if f is None else to_gpu(f),
+                        ts_count).cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == (ts_count,)
+    np.testing.assert_array_equal(got, want.astype(np.float32))
+    assert (want > 0).any() or flags == "all"
+
+
+@pytest.mark.parametrize("n", [1, 2047, 2048, 2049, 2048 * 256,
+                               2048 * 256 + 1, 2048 * 300 + 5])
+def test_inclusive_scan_exact(C, n):
+    """More than 256 blocks of 2048 take the serial-chunk branch of the
+    block-sums kernel.  Every partial sum of the scan is the sum of a
+    contiguous range, a difference of two cumulative sums."""
+    rng = np.random.default_rng(n)
+    x = rng.integers(-3, 4, size=n).astype(np.float32)
+    want = np.cumsum(x.astype(np.float64))
+    assert np.abs(want).max() < 2 ** 23
+    got = C.inclusive_scan(to_gpu(x)).cpu().numpy()
+    np.testing.assert_array_equal(got, want.astype(np.float32))
+
+
+LADDER_LENGTHS = [2 << k for k in range(12)]  # 2 .. 4096, the kernel's 12
+
+
+@pytest.mark.parametrize("ts_count", [5, 64, 2049, 300001])
+def test_boxcar_ladder(C, ts_count):
+    """Integer series with planted spikes: every box value is an exact
+    integer.  Lengths >= ts_count (and == ts_count at 64) have no window."""
+    snr = 6.0
+    rng = np.random.default_rng(ts_count)
+    ts = rng.integers(-3, 4, size=ts_count).astype(np.float64)
+    for pos, amp in [(3, 60), (ts_count // 2, 100), (ts_count - 2, 250)]:
+        ts[pos] += amp
+        ts[(pos * 7 + 1) % ts_count:][:9] += amp // 10  # a wide, low one
+    cum = np.cumsum(ts)
+    assert np.abs(cum).max() < 2 ** 23
+    thr, counts = C.boxcar_ladder(to_gpu(cum.astype(np.float32)),
+                                  LADDER_LENGTHS, snr)
+    thr, counts = thr.cpu().numpy(), counts.cpu().numpy()
+    assert thr.dtype == np.float32 and counts.dtype == np.int32
+    assert thr.shape == counts.shape == (12,)
+    seen = 0
+    for k, b in enumerate(LADDER_LENGTHS):
+        if b >= ts_count:
+            assert counts[k] == 0, (b, counts[k])
+            continue
+        box = cum[b:] - cum[:-b]
+        want = np.float32(snr) * np.float32(np.sqrt((box * box).sum()
+                                                    / box.size))
+        assert abs(float(thr[k]) - float(want)) <= 2 * U * float(want), \
+            (b, thr[k], want)
+        n = int((box.astype(np.float32) > thr[k]).sum())
+        assert counts[k] == n, (b, counts[k], n)
+        seen += n
+    # (a series of a few dozen samples cannot hold a 6-sigma window)
+    assert seen > 0 or ts_count < 2049
+
+
+@pytest.mark.parametrize("rows,length", [(5, 513), (3, 2), (4, 1)])
+def test_sk_row_stats_exact(C, rows, length):
+    """An odd length takes the scalar kernel (rows are not 16-byte aligned);
+    length 2 is one float4 per row."""
+    wf = int_waterfall(rows, length, 3, seed=length)
+    p = wf.real.astype(np.float64) ** 2 + wf.imag.astype(np.float64) ** 2
+    s2, s4 = p.sum(axis=1), (p * p).sum(axis=1)
+    assert s4.max() < 2 ** 24
+    got = C.sk_row_stats(to_gpu(wf)).cpu().numpy()
+    np.testing.assert_array_equal(got[:, 0], s2.astype(np.float32))
+    np.testing.assert_array_equal(got[:, 1], s4.astype(np.float32))
+
+
+# The final DIF pass of a length-L plan runs n-point transforms, F to a
+# workgroup; workgroup w of a row stores the columns J + k L/n with
+# J in [w F, (w + 1) F) and k in [0, n): the first is w F, the last
+# L - L/n + w F + F - 1.
+#   L = 8192:  n = 256, F = 16, 2 workgroups per row:
+#              first 0, 16; last 8175, 8191
+#   L = 16384: n = 64, F = 32, 8 workgroups per row:
+#              first 0, 32, ..., 224; last 16159, 16191, ..., 16383
+#   L = 4096:  the single-pass DIF, one workgroup per row (not an engine
+#              shape: the waterfall FFT takes the wave kernel below 4096 and
+#              column passes above)
+DIF_SHAPE = {8192: (256, 16), 16384: (64, 32), 4096: (4096, 1)}
+
+
+@pytest.mark.parametrize("rows,L", [(64, 8192), (64, 16384), (8, 4096)])
+def test_native_fft_sk_owns_every_element_once(C, rows, L):
+    """Row r is a tone whose backward transform is one spike of size L at
+    column j_r: a workgroup of the DIF epilogue that drops or doubles the
+    column, or a partial that lands in another row, changes that row's sums
+    by a factor of order 1."""
+    n, F = DIF_SHAPE[L]
+    wgs = L // n // F
+    cols = [0, 1, 255, 256, L // 2 - 1, L // 2, L - 1]
+    for w in range(wgs):
+        cols += [w * F, L - L // n + w * F + F - 1]
+    cols = list(dict.fromkeys(cols))[:rows]
+    rng = np.random.default_rng(L)
+    j = np.array(cols + list(rng.integers(0, L, size=rows - len(cols))))
+    k = np.arange(L)
+    x = np.exp(-2j * np.pi * ((j[:, None] * k[None, :]) % L) / L)
+    x += 1e-3 * (rng.normal(size=(rows, L)) + 1j * rng.normal(size=(rows, L)))
+    xt = to_gpu(x.astype(np.complex64))
+    out, stats = C.native_fft_sk(xt)
+    out, stats = out.cpu().numpy(), stats.cpu().numpy().astype(np.float64)
+    plain = C.native_fft(xt, 1).cpu().numpy()
+    assert np.array_equal(out.view(np.uint32), plain.view(np.uint32))
+    assert np.array_equal(np.abs(out).argmax(axis=1), j)
+    p = out.real.astype(np.float64) ** 2 + out.imag.astype(np.float64) ** 2
+    s2, s4 = p.sum(axis=1), (p * p).sum(axis=1)
+    assert (s2 > 0.9 * L * L).all()
+    r2 = np.abs(stats[:, 0] - s2) / s2 / ((L + 4) * U)
+    r4 = np.abs(stats[:, 1] - s4) / s4 / ((L + 8) * U)
+    print(f"L {L}: max |err| / bound: s2 {r2.max():.4f} s4 {r4.max():.4f}")
+    assert r2.max() <= 1.0 and r4.max() <= 1.0, (r2, r4)
+
+
+def test_native_fft_sk_rejects_a_plan_without_epilogue(C):
+    x = torch.zeros(4, 1024, dtype=torch.complex64).cuda()
+    with pytest.raises(RuntimeError):  # the wave kernel has no SK epilogue
+        C.native_fft_sk(x)
+
+
 # ---------------- display ----------------
 
 def test_resample_power(C):
