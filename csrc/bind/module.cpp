@@ -695,11 +695,28 @@ torch::Tensor t_native_rfft(torch::Tensor x) {
   auto packed = x.view({(int64_t)m, 2});  // reinterpret as complex pairs
   auto work = torch::empty_like(z);
   work.copy_(torch::view_as_complex(packed));
-  plan.exec(cptr(work), cptr(z), stream);
-  check(r2c_post_process(cptr(z), cptr(z), m, nullptr, nullptr, stream),
-        "r2c post");
+  if (plan.r2c_final_partials()) {
+    // the final pass combines the (k, m-k) pairs at its store
+    const NativeFft::R2cFinal rf;
+    plan.exec(cptr(work), cptr(z), stream, nullptr, nullptr, nullptr, 2,
+              nullptr, &rf);
+  } else {
+    plan.exec(cptr(work), cptr(z), stream);
+    check(r2c_post_process(cptr(z), cptr(z), m, nullptr, nullptr, stream),
+          "r2c post");
+  }
   check(hipStreamSynchronize(stream), "native_rfft sync");
   return z;
+}
+
+int64_t t_native_rfft_final_partials(int64_t n) {
+  // what native_rfft's plan for n real samples reports: > 0 = its final pass
+  // does the r2c pair-combine (and would write that many mean partials)
+  auto stream = cur_stream();
+  NativeFft plan;
+  plan.plan((size_t)n / 2, 1, -1, stream);
+  check(hipStreamSynchronize(stream), "native_rfft plan sync");
+  return plan.r2c_final_partials();
 }
 
 // ---------------- FFT microbenchmarks (plan once, event-timed) ----------------
@@ -767,9 +784,16 @@ double t_bench_rfft(int64_t n, int64_t iters, std::string backend) {
     const size_t m = n / 2;
     NativeFft plan;
     plan.plan(m, 1, -1, stream);
+    const bool fused = plan.r2c_final_partials() != 0;
+    const NativeFft::R2cFinal rf;
     ms = time_iters(stream, (int)iters, [&] {
-      plan.exec(reinterpret_cast<float2*>(xp), yp, stream);
-      check(r2c_post_process(yp, yp, m, nullptr, nullptr, stream), "post");
+      if (fused) {
+        plan.exec(reinterpret_cast<float2*>(xp), yp, stream, nullptr, nullptr,
+                  nullptr, 2, nullptr, &rf);
+      } else {
+        plan.exec(reinterpret_cast<float2*>(xp), yp, stream);
+        check(r2c_post_process(yp, yp, m, nullptr, nullptr, stream), "post");
+      }
     });
   } else {
     hipfftHandle h;
@@ -1143,6 +1167,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("native_fft", &t_native_fft, py::arg("x"), py::arg("sign"));
   m.def("native_fft_sk", &t_native_fft_sk, py::arg("x"));
   m.def("native_rfft", &t_native_rfft, py::arg("x"));
+  m.def("native_rfft_final_partials", &t_native_rfft_final_partials,
+        py::arg("n"));
   m.def("preop_backward_fft", &t_preop_backward_fft, py::arg("spec"),
         py::arg("maxcol_log2"), py::arg("final_log2"), py::arg("f_min"),
         py::arg("f_c"), py::arg("df"), py::arg("dms"),

@@ -268,6 +268,12 @@ PipelineEngine::PipelineEngine(const EngineConfig& cfg, int n_slots)
     fuse_r2c_ = false;
     if (native_fft_) {
       s.nfwd.plan(nc_, 1, -1, s.stream);
+      // r2c pair-combine at the forward final pass's store (default where
+      // the plan allows it, SRTB_FFT_R2C_FINAL=0 reverts): its mean-power
+      // partials are one per workgroup, a count that comes from the plan
+      if (const int rp = s.nfwd.r2c_final_partials())
+        check_hip(hipMalloc(&s.r2c_final_partials, rp * sizeof(double)),
+                  "r2c final partials alloc");
       if (native_bwd_) {
         // the RFI+dedispersion preop fuses into the backward's FIRST
         // pass; SRTB_FFT_BWD32=1 plans it 32-max-column + final-256 (the
@@ -358,6 +364,7 @@ PipelineEngine::~PipelineEngine() {
     if (s.sk_dif_partials) (void)hipFree(s.sk_dif_partials);
     if (s.xbuf) (void)hipFree(s.xbuf);
     if (s.fwd_pw) (void)hipFree(s.fwd_pw);
+    if (s.r2c_final_partials) (void)hipFree(s.r2c_final_partials);
     (void)hipFree(s.flags);
     (void)hipFree(s.ts);
     (void)hipFree(s.ts_partial);
@@ -658,6 +665,19 @@ void PipelineEngine::enqueue_front(Slot& s, const uint8_t* dev_raw,
       check_hip(r2c_mean_from_power(s.fwd_pw, fwd_pw_n_, s.spec, nc_,
                                     s.mean_power, st),
                 "r2c mean");
+  } else if (native_fft_ && s.r2c_final_partials) {
+    // 2. forward transform of the packed-real view whose final pass combines
+    //    the (k, Nc-k) pairs at its store: s.spec receives the r2c spectrum
+    //    directly, with the FUSED mean-|X|^2, and the standalone r2c pass
+    //    (8.6 GB) is gone
+    NativeFft::R2cFinal rf;
+    if (cfg_.enable_rfi_s1) {
+      rf.mean_partials = s.r2c_final_partials;
+      rf.out_mean = s.mean_power;
+    }
+    s.nfwd.exec(reinterpret_cast<float2*>(s.samples), s.spec, st, nullptr,
+                nullptr, fuse_unpack ? dev_raw : nullptr, in_bits, nullptr,
+                &rf);
   } else if (native_fft_) {
     // 2. forward C2C of the packed-real view + r2c post-process with FUSED
     //    mean-|X|^2 (saves the separate 4 GB mean_power pass)

@@ -317,6 +317,8 @@ class PipelineEngine {
     float2* spec = nullptr;         // [Nc+1] spectrum / waterfall (in-place)
     float2* xbuf = nullptr;         // [Nc] bwd working set (r2c fusion)
     float2* fwd_pw = nullptr;       // fwd-DIF per-WG power partials
+    double* r2c_final_partials = nullptr;  // fused r2c store's mean partials
+                                           // (non-null = that path is taken)
     float2* s2s4 = nullptr;         // [S]
     float2* sk_dif_partials = nullptr;  // [S * wgs_per_row] (fused SK stats)
     uint8_t* flags = nullptr;       // [S]

@@ -3,7 +3,9 @@
 // Plans pow2 C2C transforms as 1-3 Stockham passes (each pass length <=
 // kMaxPassLen) with fused inter-pass twiddles and transpose-free output
 // scatter; real-input forward transforms use the packed-complex trick +
-// r2c_post_process.  Index math: srtb_amd/fftref.py (fft_deep).
+// r2c_post_process, or the pair-combine at the final pass's store
+// (r2c_final_partials()).  Index math: srtb_amd/fftref.py (fft_deep,
+// r2c_final_store).
 //
 // Buffer discipline: every pass except the last is in-place safe (a pass
 // writes exactly the locations it read, workgroup-locally staged through
@@ -69,6 +71,11 @@ class NativeFft {
     len_ = len;
     batch_ = batch;
     sign_ = sign;
+    // SRTB_FFT_R2C_FINAL=0: never fold the r2c pair-combine into the final
+    // pass (r2c_final_partials() then reports 0)
+    const char* rf = std::getenv("SRTB_FFT_R2C_FINAL");
+    r2c_final_ = !(rf && std::atoi(rf) == 0);
+    r2c_f_ = 0;
 
     const size_t L = len;
     // Decomposition (see csrc/kernels/fft.hip):
@@ -249,6 +256,9 @@ class NativeFft {
       p.n_ffts = batch * (L / fn);
       p.tw_n = len_table(fn);
       passes_.push_back(p);
+      // fixed here, not per call: the caller sizes its partials buffer from
+      // r2c_final_partials()
+      r2c_f_ = dif_r2c_f(p);
     }
   }
 
@@ -280,9 +290,31 @@ class NativeFft {
     return (int)(per_row / F);
   }
 
+  // The r2c pair-combine of a packed-real forward transform can fold into
+  // the final DIF pass's store (fft_dif_final_r2c): sign -1, batch 1, a
+  // composite plan whose last pass is the DIF one, at least 2F instances,
+  // and SRTB_FFT_R2C_FINAL not 0 at plan time.  Returns the number of
+  // mean-power partials (doubles) that pass writes, or 0 when the fusion
+  // does not apply and the caller runs r2c_post_process after exec().
+  int r2c_final_partials() const {
+    if (!r2c_final_ || sign_ != -1 || batch_ != 1 || passes_.size() < 2 ||
+        passes_.back().kind != PassKind::kDif)
+      return 0;
+    const Pass& p = passes_.back();
+    return fft_dif_final_r2c_wgs(p.n_ffts, r2c_f_);
+  }
+
+  // mean|X|^2 outputs of the fused r2c store; both null = spectrum only
+  struct R2cFinal {
+    double* mean_partials = nullptr;  // r2c_final_partials() doubles
+    double* out_mean = nullptr;
+  };
+
   // Execute the planned transform.  out may equal in only for 1-pass plans.
   // preop (optional) is applied to the FIRST pass's loads (requires
   // first_pass_fusable()).
+  // r2c_final (optional, requires r2c_final_partials() > 0): the final pass
+  // writes the r2c spectrum of the packed-real input instead of the C2C one.
   // first_pass_out (optional): write the FIRST column pass out-of-place
   // into this buffer (later passes continue in place there).  REQUIRED
   // when preop->r2c_m is set: the pair-combine reads element m-k of the
@@ -291,8 +323,11 @@ class NativeFft {
             const FftPreop* preop = nullptr,
             float2* dif_sk_partials = nullptr,
             const uint8_t* decode2_raw = nullptr, int decode_bits = 2,
-            float2* first_pass_out = nullptr) {
+            float2* first_pass_out = nullptr,
+            const R2cFinal* r2c_final = nullptr) {
     if (passes_.empty()) throw std::runtime_error("NativeFft: not planned");
+    if (r2c_final && (r2c_final_partials() == 0 || dif_sk_partials))
+      throw std::runtime_error("NativeFft: r2c final-pass fusion n/a");
     if (passes_.size() > 1 && in == out && !first_pass_out)
       throw std::runtime_error("NativeFft: multi-pass needs out != in");
     if (preop && preop->r2c_m && !first_pass_out)
@@ -337,6 +372,14 @@ class NativeFft {
                     "fft_wave_pass");
           break;
         case PassKind::kDif: {
+          if (last && r2c_final) {
+            check_hip(fft_dif_final_r2c(cur, dst, p.dif, p.n_ffts,
+                                        r2c_f_, p.tw_n,
+                                        r2c_final->mean_partials,
+                                        r2c_final->out_mean, stream),
+                      "fft_dif_final_r2c");
+            break;
+          }
           const int F = dif_f(p);
           check_hip(fft_dif_final(cur, dst, p.dif, p.n_ffts, F, sign_,
                                   p.tw_n, dif_sk_partials, stream),
@@ -399,6 +442,26 @@ class NativeFft {
                80 * 1024)
       F >>= 1;
     while (F > 1 && p.n_ffts % F != 0) F >>= 1;
+    return F;
+  }
+
+  // instances per SIDE of the fused r2c final pass, which holds 2F rows in
+  // LDS (own + mirror instances): same LDS target and override as dif_f;
+  // SRTB_FFT_R2C_F overrides this pass alone (A/B against the backward
+  // plan's unchanged final pass)
+  int dif_r2c_f(const Pass& p) const {
+    int F = (p.dif.n <= 64) ? 32 : 16;
+    for (const char* name : {"SRTB_FFT_DIF_F", "SRTB_FFT_R2C_F"}) {
+      if (const char* e = std::getenv(name)) {
+        const int v = std::atoi(e);
+        if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) F = v;
+      }
+    }
+    while (F > 1 &&
+           ((size_t)p.dif.n + 2 * (size_t)F * (p.dif.n + 2)) * sizeof(float2) >
+               80 * 1024)
+      F >>= 1;
+    while (F > 1 && p.n_ffts % (2 * (size_t)F) != 0) F >>= 1;
     return F;
   }
 
@@ -473,6 +536,8 @@ class NativeFft {
 
   size_t len_ = 0, batch_ = 0;
   int sign_ = -1;
+  bool r2c_final_ = true;
+  int r2c_f_ = 0;  // instances per side of the fused r2c final pass
   std::vector<Pass> passes_;
   std::vector<Table> tables_;
 };

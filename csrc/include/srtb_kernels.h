@@ -379,6 +379,20 @@ hipError_t fft_dif_final(const float2* in, float2* out, const DifFinalDesc& d,
                          size_t n_ffts, int F, int sign, const float2* tw_n,
                          float2* sk_partials, hipStream_t stream);
 
+// Forward final pass of a batch-1 packed-real transform with the r2c
+// pair-combine folded into its store: out receives the ordinary r2c
+// spectrum X[0..M) (what fft_dif_final followed by r2c_post_process gives,
+// bit for bit) and the packed spectrum Z is never written.  F instances per
+// side and workgroup (2F rows in LDS); needs out != in, sign -1, a composite
+// plan (n_prefix >= 1) and P = n_ffts = M/n >= 2F.
+// mean_partials (optional, fft_dif_final_r2c_wgs(n_ffts, F) doubles): also
+// writes mean|X|^2 to out_mean, one deterministic partial per workgroup.
+int fft_dif_final_r2c_wgs(size_t n_ffts, int F);  // 0: does not apply
+hipError_t fft_dif_final_r2c(const float2* in, float2* out,
+                             const DifFinalDesc& d, size_t n_ffts, int F,
+                             const float2* tw_n, double* mean_partials,
+                             double* out_mean, hipStream_t stream);
+
 // combine the DIF-written partials into per-row <S2,S4>
 hipError_t sk_combine_partials(const float2* partials, size_t rows,
                                int wgs_per_row, float2* s2s4,

@@ -5,7 +5,8 @@
 //  - four-step composite passes: strided column FFTs with fused inter-pass
 //    twiddles (split-table exact), and row FFTs whose digit-reversal output
 //    scatter replaces rocFFT's separate transpose kernels entirely,
-//  - the r2c post-process (packed-real trick) as a separate small kernel.
+//  - the r2c post-process (packed-real trick) as a separate small kernel, or
+//    folded into the store of the forward final pass (k_fft_dif_final_r2c).
 //
 // Index math is the NumPy oracle in srtb_amd/fftref.py (fft_small_r4 /
 // fft_four_step / fft_deep / r2c_post); conventions are cuFFT's (forward
@@ -1295,6 +1296,30 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// The pair-combine itself, shared by k_r2c_post and the fused final pass
+// (k_fft_dif_final_r2c) so that both write the same bits: zk = Z[k],
+// zm = Z[M-k], phiw = -pi k / M; xk = X[k], xm = X[M-k].
+// The rotation w*O is spelled with explicit fmas, in exactly the form the
+// compiler contracts cmulf(w, odd) to inside k_r2c_post (one rounded product
+// feeding one fma per component), so the result does not depend on what
+// either kernel's surrounding code lets the contraction pass see.  The
+// remaining operations are exact scalings by 0.5 and single additions.
+__device__ __forceinline__ void r2c_pair_combine(float2 zk, float2 zm,
+                                                 float phiw, float2& xk,
+                                                 float2& xm) {
+  const float2 zmc = make_float2(zm.x, -zm.y);
+  const float2 even = make_float2(0.5f * (zk.x + zmc.x),
+                                  0.5f * (zk.y + zmc.y));
+  const float2 dif = make_float2(zk.x - zmc.x, zk.y - zmc.y);
+  const float2 odd = make_float2(0.5f * dif.y, -0.5f * dif.x);
+  float sw, cw;
+  __sincosf(phiw, &sw, &cw);
+  const float2 wo = make_float2(__builtin_fmaf(cw, odd.x, -(sw * odd.y)),
+                                __builtin_fmaf(cw, odd.y, sw * odd.x));
+  xk = make_float2(even.x + wo.x, even.y + wo.y);
+  xm = make_float2(even.x - wo.x, -(even.y - wo.y));
+}
+
 template <bool MEANP>
 __global__ void k_r2c_post(const float2* __restrict__ z,
                            float2* __restrict__ x, size_t m,
@@ -1306,22 +1331,13 @@ __global__ void k_r2c_post(const float2* __restrict__ z,
        k += stride) {
     const float2 zk = z[k];
     const float2 zm = z[k == 0 ? 0 : m - k];
-    const float2 zmc = make_float2(zm.x, -zm.y);
-    const float2 even = make_float2(0.5f * (zk.x + zmc.x),
-                                    0.5f * (zk.y + zmc.y));
-    const float2 dif = make_float2(zk.x - zmc.x, zk.y - zmc.y);
-    const float2 odd = make_float2(0.5f * dif.y, -0.5f * dif.x);
     // argument reduced in fp64 (k/m exact), fast f32 sincos (~1.5e-6 rad)
     const float phiw = (float)(-M_PI * (double)k / (double)m);
-    float sw, cw;
-    __sincosf(phiw, &sw, &cw);
-    const float2 w = make_float2(cw, sw);
-    const float2 wo = cmulf(w, odd);
-    const float2 xk = make_float2(even.x + wo.x, even.y + wo.y);
+    float2 xk, xm;
+    r2c_pair_combine(zk, zm, phiw, xk, xm);
     x[k] = xk;
     if constexpr (MEANP) acc += (double)xk.x * xk.x + (double)xk.y * xk.y;
     if (k != 0 && k != half) {
-      const float2 xm = make_float2(even.x - wo.x, -(even.y - wo.y));
       x[m - k] = xm;
       if constexpr (MEANP)
         acc += (double)xm.x * xm.x + (double)xm.y * xm.y;
@@ -1340,6 +1356,209 @@ __global__ void k_r2c_post_finish_mean(const double* __restrict__ partials,
   for (int i = threadIdx.x; i < np; i += blockDim.x) acc += partials[i];
   const double b = block_reduce_sum(acc);
   if (threadIdx.x == 0) *out_mean = b / (double)n;
+}
+
+// ---------------------------------------------------------------------------
+// Forward final pass with the r2c pair-combine folded into its store
+// (batch 1, packed length M = row_len, P = M/n instances; index model:
+// fftref.r2c_final_store).  k_fft_dif_final writes element k of instance J to
+// o = J + k*P, and M - o = (P-J) + (n-1-k)*P: instance J pairs with instance
+// P-J as a whole.  Workgroup w owns J in [wF+1, wF+F] (LDS rows 0..F-1) and
+// the mirror instances P-J (rows F..2F-1), so both partners of every pair
+// sit in its LDS and the packed spectrum Z never reaches memory.  The last
+// of these workgroups holds the self-paired instance P/2 on both sides; one
+// extra workgroup (the last of the grid) transforms instance 0 alone, whose
+// element k pairs with its own element n-k.
+// Driver rule: the element of a pair with the smaller output index
+// ko <= M/2 computes both X[ko] and X[M-ko], exactly as k_r2c_post's loop
+// body does at k = ko, and nobody else writes those two addresses.
+// Load, swizzle and butterflies are k_fft_dif_final<-1>'s.
+// ---------------------------------------------------------------------------
+template <bool MEANP>
+__global__ void __launch_bounds__(256)
+    k_fft_dif_final_r2c(const float2* __restrict__ in,
+                        float2* __restrict__ out, DifFinalDescDev d,
+                        const float2* __restrict__ tw_n,
+                        double* __restrict__ partials, uint32_t tuning) {
+  extern __shared__ float2 lds[];
+  const int n = d.n;
+  const int nl = d.n_log2;
+  const int F = 1 << d.f_log2;  // instances per SIDE
+  const int ldst = n + 2;
+  float2* ltw = lds;
+  float2* X = lds + n;
+  const unsigned long long P = 1ull << d.j_bits;
+  const unsigned long long m = d.row_len;
+  const bool row0 = blockIdx.x == gridDim.x - 1;
+  const int rows = row0 ? 1 : 2 * F;
+  // The own side's runs start one element past an F-aligned boundary, so
+  // the first and last cache line of every run are shared with workgroup
+  // w-1 / w+1.  With the XCD remap (tuning bit 0) neighbouring w run on the
+  // same XCD and the two halves of such a line meet in one L2.
+  const unsigned int w =
+      row0 ? blockIdx.x : xcd_swizzle(blockIdx.x, gridDim.x - 1, tuning);
+  const unsigned long long j0 =
+      ((unsigned long long)w << d.f_log2) + 1;  // first own instance
+  const int total = rows << nl;
+
+  for (int j = threadIdx.x; j < n; j += blockDim.x) ltw[j] = tw_n[j];
+
+  // ---- contiguous load (register-staged chunks of 8) ----
+  auto instance_of = [&](int r) -> unsigned long long {
+    if (row0) return 0;
+    return r < F ? j0 + r : P - (j0 + (r - F));
+  };
+  {
+    const int iters = total >> 8;
+    int it = 0;
+    for (; it + 8 <= iters; it += 8) {
+      float2 tmp[8];
+      int lidx[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int e = ((it + k) << 8) + threadIdx.x;
+        const int r = e >> nl;
+        const int i = e & (n - 1);
+        unsigned long long in_blk, obase;
+        dif_addr(instance_of(r), d, in_blk, obase);
+        tmp[k] = in[in_blk + i];
+        lidx[k] = r * ldst + dif_swz(i);
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) X[lidx[k]] = tmp[k];
+    }
+    for (int e = (it << 8) + threadIdx.x; e < total; e += blockDim.x) {
+      const int r = e >> nl;
+      const int i = e & (n - 1);
+      unsigned long long in_blk, obase;
+      dif_addr(instance_of(r), d, in_blk, obase);
+      X[r * ldst + dif_swz(i)] = in[in_blk + i];
+    }
+  }
+  __syncthreads();
+
+  // ---- in-place radix-4 DIF stages (forward) ----
+  const int quarter = n >> 2;
+  for (int L = n, tl = 0; L >= 4; L >>= 2, tl += 2) {
+    const int M = L >> 2;
+    const int m_log2 = (nl - tl) - 2;  // log2(M)
+    for (int b = threadIdx.x; b < rows * quarter; b += blockDim.x) {
+      const int r = b >> (nl - 2);
+      const int bb = b & (quarter - 1);
+      const int j = bb & (M - 1);
+      const int g = (bb >> m_log2) << (m_log2 + 2);
+      float2* row = X + r * ldst;
+      const int e0 = dif_swz(g + j);
+      const int e1 = dif_swz(g + j + M);
+      const int e2 = dif_swz(g + j + 2 * M);
+      const int e3 = dif_swz(g + j + 3 * M);
+      const float2 a = row[e0];
+      const float2 bv = row[e1];
+      const float2 c = row[e2];
+      const float2 dv = row[e3];
+      const float2 t0 = make_float2(a.x + c.x, a.y + c.y);
+      const float2 t1 = make_float2(a.x - c.x, a.y - c.y);
+      const float2 t2 = make_float2(bv.x + dv.x, bv.y + dv.y);
+      const float2 dmy = make_float2(bv.x - dv.x, bv.y - dv.y);
+      const float2 t3 = make_float2(dmy.y, -dmy.x);
+      const float2 x0 = make_float2(t0.x + t2.x, t0.y + t2.y);
+      const float2 x1 = make_float2(t1.x + t3.x, t1.y + t3.y);
+      const float2 x2 = make_float2(t0.x - t2.x, t0.y - t2.y);
+      const float2 x3 = make_float2(t1.x - t3.x, t1.y - t3.y);
+      const int ts = tl;  // W_L^x = ltw[x << tl]
+      row[e0] = x0;
+      row[e1] = (j == 0) ? x1 : cmulf(x1, ltw[(j << ts)]);
+      row[e2] = (j == 0) ? x2 : cmulf(x2, ltw[(2 * j) << ts]);
+      row[e3] = (j == 0) ? x3 : cmulf(x3, ltw[(3 * j) << ts]);
+    }
+    __syncthreads();
+  }
+
+  // ---- store: combine partner pairs out of LDS, write both results ----
+  // M is a power of two: multiplying by 1/M is the division, bit for bit
+  const double inv_m = 1.0 / (double)m;
+  const int half_n = n >> 1;
+  double acc = 0.0;
+  if (!row0) {
+    // own element (f, k) and mirror element (F + f, n-1-k) are partners;
+    // rev4(n-1-k) is the complement of rev4(k).  For fixed k the own side
+    // writes F ascending addresses and the mirror side F descending ones.
+    for (int e = threadIdx.x; e < (F << nl); e += blockDim.x) {
+      const int f = e & (F - 1);
+      const int k = e >> d.f_log2;
+      const unsigned long long J = j0 + f;
+      const bool low = k < half_n;  // the own element has the smaller index
+      // instance P/2 is on both sides: its pairs are driven from k < n/2 only
+      if (J == (P >> 1) && !low) continue;
+      const unsigned rk = rev4_bits((unsigned)k, nl);
+      const float2 own = X[f * ldst + dif_swz((int)rk)];
+      const float2 mir =
+          X[(F + f) * ldst + dif_swz((int)(rk ^ (unsigned)(n - 1)))];
+      const unsigned long long ko =
+          low ? J + (unsigned long long)k * P
+              : (P - J) + (unsigned long long)(n - 1 - k) * P;
+      const float phiw = (float)(-M_PI * (double)ko * inv_m);
+      float2 xk, xm;
+      r2c_pair_combine(low ? own : mir, low ? mir : own, phiw, xk, xm);
+      out[ko] = xk;
+      out[m - ko] = xm;
+      if constexpr (MEANP) {
+        acc += (double)xk.x * xk.x + (double)xk.y * xk.y;
+        acc += (double)xm.x * xm.x + (double)xm.y * xm.y;
+      }
+    }
+  } else {
+    // instance 0: element k pairs with element n-k; k = 0 stands alone
+    // (X[0] = Re Z0 + Im Z0) and k = n/2 (output M/2) is its own partner
+    for (int k = threadIdx.x; k <= half_n; k += blockDim.x) {
+      const float2 zk = X[dif_swz((int)rev4_bits((unsigned)k, nl))];
+      const float2 zm =
+          X[dif_swz((int)rev4_bits((unsigned)(k == 0 ? 0 : n - k), nl))];
+      const unsigned long long ko = (unsigned long long)k * P;
+      const float phiw = (float)(-M_PI * (double)ko * inv_m);
+      float2 xk, xm;
+      r2c_pair_combine(zk, zm, phiw, xk, xm);
+      out[ko] = xk;
+      if constexpr (MEANP) acc += (double)xk.x * xk.x + (double)xk.y * xk.y;
+      if (k != 0 && k != half_n) {
+        out[m - ko] = xm;
+        if constexpr (MEANP)
+          acc += (double)xm.x * xm.x + (double)xm.y * xm.y;
+      }
+    }
+  }
+  if constexpr (MEANP) {
+    // one double per workgroup, no atomics: the mean is deterministic
+    const double b = block_reduce_sum(acc);
+    if (threadIdx.x == 0) partials[row0 ? blockIdx.x : w] = b;
+  }
+}
+
+// Mean from the fused final pass's partials.  There is one per workgroup,
+// P/2F + 1 of them (131073 at the 2^30-sample block): k_r2c_post_finish_mean's
+// 256 threads with one load in flight each took 0.21 ms over them.  1024
+// threads with 8 independent loads each; the order is fixed, so the mean is
+// the same from run to run.
+__global__ void __launch_bounds__(1024)
+    k_r2c_final_finish_mean(const double* __restrict__ partials, int np,
+                            size_t n, double* __restrict__ out_mean) {
+  __shared__ double wsum[1024 / 64];
+  double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int i = threadIdx.x;
+  for (; i + 7 * 1024 < np; i += 8 * 1024) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a[u] += partials[i + u * 1024];
+  }
+  for (; i < np; i += 1024) a[0] += partials[i];
+  const double acc = wave_reduce_sum(((a[0] + a[1]) + (a[2] + a[3])) +
+                                     ((a[4] + a[5]) + (a[6] + a[7])));
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int k = 0; k < 1024 / 64; ++k) t += wsum[k];
+    *out_mean = t / (double)n;
+  }
 }
 
 constexpr int kR2cPostBlocks = 1024;
@@ -1919,6 +2138,61 @@ hipError_t fft_dif_final(const float2* in, float2* out,
     else
       hipLaunchKernelGGL((k_fft_dif_final<1, false>), dim3(grid), dim3(256),
                          lds_bytes, stream, in, out, d, tw_n, nullptr, 0);
+  }
+  SRTB_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+int fft_dif_final_r2c_wgs(size_t n_ffts, int F) {
+  if (F < 1 || n_ffts < 2 * (size_t)F || n_ffts % (2 * (size_t)F) != 0)
+    return 0;
+  return (int)(n_ffts / (2 * (size_t)F)) + 1;
+}
+
+hipError_t fft_dif_final_r2c(const float2* in, float2* out,
+                             const DifFinalDesc& hd, size_t n_ffts, int F,
+                             const float2* tw_n, double* mean_partials,
+                             double* out_mean, hipStream_t stream) {
+  if (hd.n & (hd.n - 1)) return hipErrorInvalidValue;
+  if (in == out || hd.n_prefix < 1) return hipErrorInvalidValue;
+  DifFinalDescDev d;
+  d.n = hd.n;
+  d.n_log2 = ilog2(hd.n);
+  if (d.n_log2 & 1) return hipErrorInvalidValue;  // pure radix-4 lengths only
+  if (F & (F - 1)) return hipErrorInvalidValue;
+  d.f_log2 = ilog2((unsigned)F);
+  d.row_len = hd.out_c2;  // M
+  d.out_elem_coef = hd.out_elem_coef;
+  d.n_prefix = hd.n_prefix;
+  int jb = 0;
+  for (int i = 0; i < 4; ++i) {
+    d.pf_bits[i] = hd.pf_bits[i];
+    d.pf_coef[i] = hd.pf_coef[i];
+    if (i < hd.n_prefix) jb += hd.pf_bits[i];
+  }
+  d.j_bits = jb;
+  // batch 1 only: the P = M/n instances are all of them, and M is a power
+  // of two (the kernel multiplies by 1/M)
+  if (n_ffts != (1ull << jb) || n_ffts * hd.n != hd.out_c2)
+    return hipErrorInvalidValue;
+  const int grid = fft_dif_final_r2c_wgs(n_ffts, F);
+  if (grid == 0) return hipErrorInvalidValue;
+  const size_t lds_bytes =
+      ((size_t)hd.n + 2 * (size_t)F * (hd.n + 2)) * sizeof(float2);
+  if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+  // SRTB_FFT_R2C_XCD=0: no XCD remap of the pair workgroups
+  const char* xe = std::getenv("SRTB_FFT_R2C_XCD");
+  const uint32_t tuning = (xe && std::atoi(xe) == 0) ? 0u : 1u;
+  if (mean_partials) {
+    hipLaunchKernelGGL((k_fft_dif_final_r2c<true>), dim3(grid), dim3(256),
+                       lds_bytes, stream, in, out, d, tw_n, mean_partials,
+                       tuning);
+    hipLaunchKernelGGL(k_r2c_final_finish_mean, dim3(1), dim3(1024), 0,
+                       stream, mean_partials, grid, (size_t)hd.out_c2,
+                       out_mean);
+  } else {
+    hipLaunchKernelGGL((k_fft_dif_final_r2c<false>), dim3(grid), dim3(256),
+                       lds_bytes, stream, in, out, d, tw_n, nullptr, tuning);
   }
   SRTB_CHECK_LAUNCH();
   return hipSuccess;

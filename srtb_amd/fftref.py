@@ -17,6 +17,8 @@ csrc/kernels/fft.hip implement:
  4. ``r2c_post`` — real-input FFT via the packed-complex trick: N reals are
     viewed as N/2 complex, C2C-transformed, then split into the true R2C
     spectrum (reference fft/fft_1d_r2c_post_process.hpp:33-82 capability).
+ 5. ``r2c_final_store`` / ``r2c_final_spectrum`` — the same split done at the
+    store of the forward final pass: which LDS element drives which output.
 
 Also serves as the "naive FFT" debug fallback of the reference
 (fft/naive_fft.hpp K8-K11 in SURVEY.md §2b).
@@ -223,7 +225,7 @@ def fft_deep(x: np.ndarray, factors: list[int], sign: int) -> np.ndarray:
         fft2=lambda v: fft_deep(v, factors[1:], sign).astype(np.complex128))
 
 
-def r2c_post(z: np.ndarray, sign: int = -1) -> np.ndarray:
+def r2c_post(z: np.ndarray, sign: int = -1, dtype=np.complex64) -> np.ndarray:
     """Packed-real R2C: given Z = C2C_fft(x_even + i*x_odd) of length M=N/2,
     recover the true R2C spectrum X[0..M-1] (Nyquist dropped, matching the
     pipeline's spectrum count Nc = N/2).
@@ -239,7 +241,82 @@ def r2c_post(z: np.ndarray, sign: int = -1) -> np.ndarray:
     w = np.exp(sign * 2j * np.pi * k / (2 * m))
     even = 0.5 * (zk + zmk)
     odd = -0.5j * (zk - zmk)
-    return (even + w * odd).astype(np.complex64)
+    return (even + w * odd).astype(dtype)
+
+
+def r2c_final_store(p: int, n: int, f: int) -> dict[str, np.ndarray]:
+    """Index model of the forward final pass with the r2c pair-combine at its
+    store (csrc/kernels/fft.hip k_fft_dif_final_r2c): packed length M = p*n,
+    p instances of the final length n, f instances per side and workgroup.
+
+    The plain final pass writes element k of instance J to o = J + k*p, and
+    M - o = (p - J) + (n-1-k)*p, so instance J pairs with instance p - J as
+    a whole.  Workgroup w in [0, p/2f) holds 2f LDS rows: row r < f is
+    instance w*f + 1 + r, row f + r its mirror p - (w*f + 1 + r); the last of
+    them has the self-paired instance p/2 on both sides.  Workgroup p/2f
+    holds instance 0 alone (row 0), whose element k pairs with element n-k.
+    Driver rule: of a pair, the element with the smaller output index
+    ko <= M/2 computes X[ko] and X[M-ko]; nobody else writes those.
+
+    Returns one record per driver, as equal-length int64 arrays:
+      wg, row, k      the driving workgroup and its LDS element (Z[ko])
+      prow, pk        the partner's LDS element (Z[M-ko]) in the same workgroup
+      inst, pinst     the instances those two rows hold
+      ko              output index of the driver
+      pair            1 if the driver also writes M - ko (0 at ko = 0, M/2)
+    """
+    assert p >= 2 * f and p % (2 * f) == 0 and n % 2 == 0
+    half = n // 2
+    rec: dict[str, list] = {key: [] for key in (
+        "wg", "row", "k", "prow", "pk", "inst", "pinst", "ko", "pair")}
+
+    def emit(**cols):
+        size = max(np.size(v) for v in cols.values())
+        for key, v in cols.items():
+            rec[key].append(np.broadcast_to(np.asarray(v, np.int64), (size,)))
+
+    kk = np.arange(n)
+    low = kk < half  # the own-side element has the smaller index
+    for w in range(p // (2 * f)):
+        for r in range(f):
+            j = w * f + 1 + r
+            sel = low if j == p // 2 else np.ones(n, bool)
+            k = kk[sel]
+            lo = low[sel]
+            emit(wg=w,
+                 row=np.where(lo, r, f + r), k=np.where(lo, k, n - 1 - k),
+                 prow=np.where(lo, f + r, r), pk=np.where(lo, n - 1 - k, k),
+                 inst=np.where(lo, j, p - j), pinst=np.where(lo, p - j, j),
+                 ko=np.where(lo, j + k * p, (p - j) + (n - 1 - k) * p),
+                 pair=1)
+    k = np.arange(half + 1)
+    emit(wg=p // (2 * f), row=0, k=k, prow=0, pk=np.where(k == 0, 0, n - k),
+         inst=0, pinst=0, ko=k * p, pair=(k != 0) & (k != half))
+    return {key: np.concatenate(v) for key, v in rec.items()}
+
+
+def r2c_final_spectrum(z: np.ndarray, n: int, f: int) -> np.ndarray:
+    """The r2c spectrum as the fused final pass produces it, in complex128:
+    z is the packed C2C spectrum in natural order (what the plain final pass
+    would have written: element k of instance J at J + k*p), every output is
+    computed by r2c_post's expression from the two LDS elements that
+    r2c_final_store names for it.  Outputs nobody writes stay NaN."""
+    m = z.size
+    p = m // n
+    s = r2c_final_store(p, n, f)
+    zf = np.asarray(z, dtype=np.complex128)
+    w = np.exp(-2j * np.pi * np.arange(m) / (2 * m))
+
+    def combine(a, b, idx):  # X[idx] from a = Z[idx], b = Z[M - idx]
+        return 0.5 * (a + np.conj(b)) + w[idx] * (-0.5j * (a - np.conj(b)))
+
+    zk = zf[s["inst"] + s["k"] * p]     # the LDS element (row, k)
+    zm = zf[s["pinst"] + s["pk"] * p]   # the LDS element (prow, pk)
+    out = np.full(m, np.nan + 1j * np.nan, dtype=np.complex128)
+    out[s["ko"]] = combine(zk, zm, s["ko"])
+    pair = s["pair"] == 1
+    out[m - s["ko"][pair]] = combine(zm[pair], zk[pair], m - s["ko"][pair])
+    return out
 
 
 def rfft_packed(x: np.ndarray, factors: list[int] | None = None) -> np.ndarray:
