@@ -34,6 +34,11 @@ int main(int argc, char** argv) {
     else if (a == "--count") count = (size_t)Expr::eval_int(argv[i + 1]);
     else if (a == "--offset-bytes") offset = (size_t)Expr::eval_int(argv[i + 1]);
   }
+  if (count * (size_t)std::abs(nbits) % 8 != 0) {
+    std::fprintf(stderr, "--count %zu at %d bits is not a whole number of "
+                 "bytes\n", count, nbits);
+    return 2;
+  }
   const size_t in_bytes = count * (size_t)std::abs(nbits) / 8;
 
   std::vector<uint8_t> h1(in_bytes), h2(in_bytes);

@@ -29,6 +29,18 @@ void check(hipError_t e, const char* what) { check_hip(e, what); }
 #define CHECK_CUDA(t) TORCH_CHECK((t).is_cuda(), #t " must be on GPU")
 #define CHECK_CONTIG(t) TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
 
+// the float32 window of at least `count` coefficients, or null
+const float* window_ptr(const c10::optional<torch::Tensor>& window,
+                        size_t count) {
+  if (!window.has_value()) return nullptr;
+  CHECK_CUDA(*window);
+  CHECK_CONTIG(*window);
+  TORCH_CHECK(window->scalar_type() == torch::kFloat32 &&
+                  (size_t)window->numel() >= count,
+              "window must be float32 with at least ", count, " coefficients");
+  return window->data_ptr<float>();
+}
+
 float2* cptr(torch::Tensor& t) {
   return reinterpret_cast<float2*>(t.data_ptr());
 }
@@ -40,44 +52,56 @@ torch::Tensor t_unpack(torch::Tensor raw, int64_t nbits, int64_t out_count,
                        c10::optional<torch::Tensor> window) {
   CHECK_CUDA(raw);
   CHECK_CONTIG(raw);
+  TORCH_CHECK(raw.scalar_type() == torch::kUInt8 && out_count >= 0);
+  const size_t need_bits = (size_t)out_count * (size_t)std::abs(nbits);
+  TORCH_CHECK((size_t)raw.numel() * 8 >= need_bits, "unpack: ", out_count,
+              " samples of ", nbits, " bits need more than the ", raw.numel(),
+              " bytes given");
   auto out = torch::empty({out_count},
                           raw.options().dtype(torch::kFloat32));
-  const float* w = nullptr;
-  if (window.has_value()) {
-    CHECK_CUDA(*window);
-    w = window->data_ptr<float>();
-  }
+  const float* w = window_ptr(window, (size_t)out_count);
   check(unpack(raw.data_ptr<uint8_t>(), out.data_ptr<float>(), out_count,
                (int)nbits, w, cur_stream()),
         "unpack");
   return out;
 }
 
-std::vector<torch::Tensor> t_unpack_2pol(torch::Tensor raw, std::string kind) {
+std::vector<torch::Tensor> t_unpack_2pol(torch::Tensor raw, std::string kind,
+                                         c10::optional<torch::Tensor> window) {
   CHECK_CUDA(raw);
   CHECK_CONTIG(raw);
+  TORCH_CHECK(raw.element_size() == 1 && raw.numel() % 2 == 0,
+              "unpack_2pol: raw must be an even number of bytes");
   const size_t per_pol = raw.numel() / 2;
+  const float* w = window_ptr(window, per_pol);
   auto o0 = torch::empty({(int64_t)per_pol}, raw.options().dtype(torch::kFloat32));
   auto o1 = torch::empty({(int64_t)per_pol}, raw.options().dtype(torch::kFloat32));
   auto* p = reinterpret_cast<const int8_t*>(raw.data_ptr());
   if (kind == "interleave")
     check(unpack_interleaved_2pol(p, o0.data_ptr<float>(), o1.data_ptr<float>(),
-                                  per_pol, nullptr, cur_stream()),
+                                  per_pol, w, cur_stream()),
           "unpack_2pol");
   else if (kind == "naocpsr_snap1")
     check(unpack_naocpsr_snap1(p, o0.data_ptr<float>(), o1.data_ptr<float>(),
-                               per_pol, nullptr, cur_stream()),
+                               per_pol, w, cur_stream()),
           "unpack_snap1");
   else
     TORCH_CHECK(false, "unknown 2-pol kind ", kind);
   return {o0, o1};
 }
 
-std::vector<torch::Tensor> t_unpack_gznupsr(torch::Tensor raw,
-                                            int64_t n_streams) {
+std::vector<torch::Tensor> t_unpack_gznupsr(
+    torch::Tensor raw, int64_t n_streams,
+    c10::optional<torch::Tensor> window) {
   CHECK_CUDA(raw);
   CHECK_CONTIG(raw);
+  TORCH_CHECK(n_streams == 2 || n_streams == 4,
+              "unpack_gznupsr_a1: 2 or 4 streams");
+  TORCH_CHECK(raw.element_size() == 1 && raw.numel() % n_streams == 0,
+              "unpack_gznupsr_a1: raw must be a whole number of bytes per "
+              "stream");
   const size_t per = raw.numel() / n_streams;
+  const float* w = window_ptr(window, per);
   std::vector<torch::Tensor> outs;
   float* ptrs[4] = {nullptr, nullptr, nullptr, nullptr};
   for (int i = 0; i < n_streams; ++i) {
@@ -86,9 +110,21 @@ std::vector<torch::Tensor> t_unpack_gznupsr(torch::Tensor raw,
     ptrs[i] = outs.back().data_ptr<float>();
   }
   check(unpack_gznupsr_a1(raw.data_ptr<uint8_t>(), ptrs[0], ptrs[1], ptrs[2],
-                          ptrs[3], (int)n_streams, per, nullptr, cur_stream()),
+                          ptrs[3], (int)n_streams, per, w, cur_stream()),
         "unpack_gznupsr");
   return outs;
+}
+
+// the engine's window table (0 = rectangle, 1 = hann, 2 = hamming)
+torch::Tensor t_build_window(int64_t n, int64_t kind, torch::Device dev) {
+  TORCH_CHECK(n >= 0, "build_window: n must not be negative");
+  auto out = torch::empty({n}, torch::TensorOptions()
+                                   .dtype(torch::kFloat32)
+                                   .device(dev));
+  check(build_window(out.data_ptr<float>(), (size_t)n, (int)kind,
+                     cur_stream()),
+        "build_window");
+  return out;
 }
 
 torch::Tensor t_mean_power(torch::Tensor spec) {
@@ -709,6 +745,44 @@ torch::Tensor t_native_rfft(torch::Tensor x) {
   return z;
 }
 
+// native_rfft of the samples that `raw` holds at `nbits`, decoded in the
+// first column pass's loads (the engine's default front half): the same plan
+// and the same ending as native_rfft for numel * 8 / |nbits| samples, and no
+// unpacked sample buffer beyond the in-place work area.
+torch::Tensor t_native_rfft_raw(torch::Tensor raw, int64_t nbits) {
+  CHECK_CUDA(raw);
+  CHECK_CONTIG(raw);
+  TORCH_CHECK(raw.scalar_type() == torch::kUInt8);
+  const int64_t ab = std::abs(nbits);
+  TORCH_CHECK(ab == 1 || ab == 2 || ab == 4 || ab == 8 || ab == 16,
+              "native_rfft_raw: nbits must be 1, 2, 4, 8, -8, 16 or -16");
+  TORCH_CHECK(nbits > 0 || ab >= 8, "native_rfft_raw: no signed sub-byte");
+  const size_t n = (size_t)raw.numel() * 8 / (size_t)ab;
+  const size_t m = n / 2;
+  TORCH_CHECK(m >= 2 && m * 2 * (size_t)ab == (size_t)raw.numel() * 8,
+              "native_rfft_raw: raw must hold an even number of samples");
+  auto stream = cur_stream();
+  NativeFft plan;
+  plan.plan(m, 1, -1, stream);
+  TORCH_CHECK(plan.first_pass_fusable(), "native_rfft_raw: the plan for ", m,
+              " complex elements has no column first pass");
+  auto z = torch::empty({(int64_t)m},
+                        raw.options().dtype(torch::kComplexFloat));
+  auto work = torch::empty_like(z);  // written by the decoding first pass
+  const uint8_t* rp = raw.data_ptr<uint8_t>();
+  if (plan.r2c_final_partials()) {
+    const NativeFft::R2cFinal rf;
+    plan.exec(cptr(work), cptr(z), stream, nullptr, nullptr, rp, (int)nbits,
+              nullptr, &rf);
+  } else {
+    plan.exec(cptr(work), cptr(z), stream, nullptr, nullptr, rp, (int)nbits);
+    check(r2c_post_process(cptr(z), cptr(z), m, nullptr, nullptr, stream),
+          "r2c post");
+  }
+  check(hipStreamSynchronize(stream), "native_rfft_raw sync");
+  return z;
+}
+
 int64_t t_native_rfft_final_partials(int64_t n) {
   // what native_rfft's plan for n real samples reports: > 0 = its final pass
   // does the r2c pair-combine (and would write that many mean partials)
@@ -1123,8 +1197,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "srtb_amd MI355X-native kernels + pipeline engine";
   m.def("unpack", &t_unpack, py::arg("raw"), py::arg("nbits"),
         py::arg("out_count"), py::arg("window") = c10::nullopt);
-  m.def("unpack_2pol", &t_unpack_2pol);
-  m.def("unpack_gznupsr_a1", &t_unpack_gznupsr);
+  m.def("unpack_2pol", &t_unpack_2pol, py::arg("raw"), py::arg("kind"),
+        py::arg("window") = c10::nullopt);
+  m.def("unpack_gznupsr_a1", &t_unpack_gznupsr, py::arg("raw"),
+        py::arg("n_streams"), py::arg("window") = c10::nullopt);
+  m.def("build_window", &t_build_window, py::arg("n"), py::arg("kind"),
+        py::arg("device") = torch::Device(torch::kCUDA));
   m.def("mean_power", &t_mean_power);
   m.def("sum_sumsq", &t_sum_sumsq);
   m.def("rfi_s1", &t_rfi_s1);
@@ -1167,6 +1245,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("native_fft", &t_native_fft, py::arg("x"), py::arg("sign"));
   m.def("native_fft_sk", &t_native_fft_sk, py::arg("x"));
   m.def("native_rfft", &t_native_rfft, py::arg("x"));
+  m.def("native_rfft_raw", &t_native_rfft_raw, py::arg("raw"),
+        py::arg("nbits"));
   m.def("native_rfft_final_partials", &t_native_rfft_final_partials,
         py::arg("n"));
   m.def("preop_backward_fft", &t_preop_backward_fft, py::arg("spec"),

@@ -140,6 +140,10 @@ class PipelineEngine {
   // samples on the device (count = baseband_input_count).  Used for
   // multi-polarization formats whose unpack fans one packet stream out into
   // several sample streams (reference unpack_pipe.hpp:146-390).
+  // The chain starts at the FFT, so the FFT window is the caller's job: with
+  // window_kind != 0 pass samples already multiplied by
+  // build_window(count, window_kind) (the unpack launchers take it), because
+  // the engine still de-applies the waterfall window after the backward FFT.
   // wait_event (optional): the slot's stream waits on it before the chain —
   // lets an app-owned fan-out stream (H2D + unpack of the packed block)
   // feed several engines without host synchronization.

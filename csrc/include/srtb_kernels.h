@@ -20,6 +20,19 @@ namespace srtb_hip {
 // ---------------- unpack (reference unpack.hpp:43-403) ----------------
 // nbits: 1, 2, 4 = unsigned MSB-first packed; 8/-8, 16/-16, 32/-32 = u/int
 // cast.  window (nullable) multiplies out[i] by window[i] (fused FFT window).
+//
+// Counts.  A launcher covers exactly the count it is given or returns
+// hipErrorInvalidValue and launches nothing; it never drops a remainder:
+//  - unpack, 1/2/4 bits: out_count * nbits must be a multiple of 8 (whole
+//    input bytes); any number of bytes is covered.
+//  - unpack, 8/-8 bits: any out_count (whole 4-sample words, then the
+//    out_count % 4 samples after them bytewise); 16/32 bits: any out_count.
+//  - two-pol, SNAP-1 and GZNU: the count per polarization / per stream must be
+//    a multiple of 4 (one lane decodes 4 samples of every stream).
+// Alignment assumed, not checked: `in` 4-byte aligned for the sub-byte and
+// 8-bit paths (dword loads), element-aligned for the 16/32-bit casts, 8-byte
+// aligned for two-pol and SNAP-1 (uint2 loads), 4-byte aligned for GZNU;
+// every output 16-byte aligned (float4 stores); window as float.
 hipError_t unpack(const uint8_t* in, float* out, size_t out_count, int nbits,
                   const float* window, hipStream_t stream);
 
@@ -327,9 +340,10 @@ hipError_t r2c_mean_from_power(const float2* power_partials,
 // Register-resident column FFT pass (N in {2,4,8,16,32,64}; one FFT per
 // thread fully in VGPRs; in-place: out must alias layout of in addressing;
 // uses the same FftPassDesc fields; out_* ignored, stores to input layout).
-// raw2 (optional): fused sub-byte unpack (raw_bits in {1,2,4}) — the pass
-// loads and decodes raw bytes instead of reading `in` (forward first pass
-// only; requires an inter-pass twiddle and no preop).
+// raw2 (optional): fused unpack (raw_bits in {1, 2, 4, 8, -8, 16, -16}, the
+// formats of unpack() above) — the pass loads and decodes raw bytes instead
+// of reading `in`: complex element i is real samples (2i, 2i+1).  Requires
+// an inter-pass twiddle and no preop; raw2 element-aligned for 16 bits.
 hipError_t fft_col_pass(const float2* in, float2* out, const FftPassDesc& d,
                         size_t n_ffts, int sign, const float2* tw_n,
                         const float2* tw_hi, const float2* tw_lo,

@@ -121,33 +121,53 @@ __device__ inline void digits(unsigned long long id, const FftPassDescDev& d,
 // the same raw byte (MSB-first fields).  Reading 0.12-0.5 GB of bytes
 // replaces a 4 GB float re-read AND the standalone unpack kernel's 4 GB
 // write (measured +7.6%% end-to-end on the 2-bit J1644 config).
+//
+// The decoded pair leaves through dec_opaque(): an empty, non-volatile asm
+// that costs no instruction and orders nothing, but hides from the optimizer
+// that the floats were small unsigned integers.  With that visible it moved
+// the first butterflies' additions into the integer domain and then chose
+// other products to contract into FMAs than in the float-input instance, so
+// the decoded transform differed from unpack + the same transform in the
+// last bits (up to 3.2e-7 of the row's rms for the unsigned formats, enough
+// to move the engine's baseline-subtracted time series by 1.6e-3 relative
+// at 4, 8 and 16 bits).  Behind the asm both instances run one arithmetic and
+// agree bit for bit (tests/test_gpu_front_half.py).  Price: the pair64
+// decoding instances take the float instance's 136 VGPRs (3 waves/SIMD)
+// instead of 128, 0.7 % of the flagship (118.2 against 117.4 ms per 8
+// blocks, alternating runs); amdgpu_waves_per_eu(4) on them spills 40 bytes
+// and measured slower still (119.6).
+__device__ inline float2 dec_opaque(float x, float y) {
+  asm("" : "+v"(x), "+v"(y));
+  return make_float2(x, y);
+}
+
 template <int NBITS>
 __device__ inline float2 decN_load(const uint8_t* __restrict__ raw,
                                    unsigned long long flat) {
   if constexpr (NBITS == 4) {
     const uint32_t bv = raw[flat];
-    return make_float2((float)((bv >> 4) & 15u), (float)(bv & 15u));
+    return dec_opaque((float)((bv >> 4) & 15u), (float)(bv & 15u));
   } else if constexpr (NBITS == 2) {
     const uint32_t bv = raw[flat >> 1];
     const int j0 = (int)(flat & 1) * 2;
-    return make_float2((float)((bv >> ((3 - j0) * 2)) & 3u),
-                       (float)((bv >> ((2 - j0) * 2)) & 3u));
+    return dec_opaque((float)((bv >> ((3 - j0) * 2)) & 3u),
+                      (float)((bv >> ((2 - j0) * 2)) & 3u));
   } else if constexpr (NBITS == 8) {
-    return make_float2((float)raw[2 * flat], (float)raw[2 * flat + 1]);
+    return dec_opaque((float)raw[2 * flat], (float)raw[2 * flat + 1]);
   } else if constexpr (NBITS == -8) {
     const int8_t* r8 = reinterpret_cast<const int8_t*>(raw);
-    return make_float2((float)r8[2 * flat], (float)r8[2 * flat + 1]);
+    return dec_opaque((float)r8[2 * flat], (float)r8[2 * flat + 1]);
   } else if constexpr (NBITS == 16) {
     const uint16_t* r16 = reinterpret_cast<const uint16_t*>(raw);
-    return make_float2((float)r16[2 * flat], (float)r16[2 * flat + 1]);
+    return dec_opaque((float)r16[2 * flat], (float)r16[2 * flat + 1]);
   } else if constexpr (NBITS == -16) {
     const int16_t* r16 = reinterpret_cast<const int16_t*>(raw);
-    return make_float2((float)r16[2 * flat], (float)r16[2 * flat + 1]);
+    return dec_opaque((float)r16[2 * flat], (float)r16[2 * flat + 1]);
   } else {  // NBITS == 1
     const uint32_t bv = raw[flat >> 2];
     const int j0 = (int)(flat & 3) * 2;
-    return make_float2((float)((bv >> (7 - j0)) & 1u),
-                       (float)((bv >> (6 - j0)) & 1u));
+    return dec_opaque((float)((bv >> (7 - j0)) & 1u),
+                      (float)((bv >> (6 - j0)) & 1u));
   }
 }
 
@@ -1861,9 +1881,9 @@ hipError_t fft_col_pass(const float2* in, float2* out, const FftPassDesc& hd,
     COL_DISPATCH(4)
     COL_DISPATCH(8)
     COL_DISPATCH(16)
-    // N = 32: the lane-pair kernel (6 waves/SIMD) measured end-to-end
-    // neutral vs the mono kernel (3 waves) and is opt-in via
-    // SRTB_FFT_PAIR32=1 pending more soak coverage; mono is the default.
+    // N = 32: the lane-pair kernel (6 waves/SIMD) is the default, see
+    // use_pair32(); SRTB_FFT_PAIR32=0 falls back to the mono kernel
+    // (3 waves), which the suite runs in a child process.
     case 32:
       if (poly) {
         if (use_pair32())

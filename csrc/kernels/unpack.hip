@@ -141,13 +141,21 @@ __global__ void k_unpack_subbyte_w(const uint32_t* __restrict__ in,
 }
 
 // ---- byte casts: one uint32 = 4 samples per lane ----
+// n = total samples; the n % 4 samples past the last whole word are read as
+// bytes, one per thread, by the first threads of the grid.
 template <bool kSigned, bool kWindow>
 __global__ void k_unpack_cast8(const uint32_t* __restrict__ in,
-                               float* __restrict__ out, size_t n_words,
+                               float* __restrict__ out, size_t n,
                                const float* __restrict__ window) {
+  const size_t n_words = n / 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words;
-       w += stride) {
+  const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (const size_t t = n_words * 4 + t0; t < n) {
+    const uint8_t b = reinterpret_cast<const uint8_t*>(in)[t];
+    const float f = kSigned ? (float)(int8_t)b : (float)b;
+    out[t] = wmul<kWindow>(window, t, f);
+  }
+  for (size_t w = t0; w < n_words; w += stride) {
     const uint32_t v = in[w];
     const size_t base = w * 4;
     float4 o;
@@ -305,6 +313,7 @@ hipError_t unpack(const uint8_t* in, float* out, size_t out_count, int nbits,
     case 1:
     case 2:
     case 4: {
+      if (out_count * (size_t)nbits % 8 != 0) return hipErrorInvalidValue;
       const size_t n_bytes = out_count * nbits / 8;
       // main body: whole 256-byte wave blocks (dense loads); byte-per-lane
       // tail kernel covers the remainder (only for non-multiple-of-256
@@ -347,23 +356,24 @@ hipError_t unpack(const uint8_t* in, float* out, size_t out_count, int nbits,
     }
     case 8:
     case -8: {
-      const size_t n_words = out_count / 4;
-      const dim3 g = grid_for(n_words);
+      // whole words by the grid-stride loop, the out_count % 4 samples after
+      // them bytewise (grid_for launches at least one block)
+      const dim3 g = grid_for(out_count / 4);
       auto* in32 = reinterpret_cast<const uint32_t*>(in);
       if (nbits < 0) {
         if (w)
           hipLaunchKernelGGL((k_unpack_cast8<true, true>), g, dim3(kBlock), 0,
-                             stream, in32, out, n_words, window);
+                             stream, in32, out, out_count, window);
         else
           hipLaunchKernelGGL((k_unpack_cast8<true, false>), g, dim3(kBlock), 0,
-                             stream, in32, out, n_words, window);
+                             stream, in32, out, out_count, window);
       } else {
         if (w)
           hipLaunchKernelGGL((k_unpack_cast8<false, true>), g, dim3(kBlock), 0,
-                             stream, in32, out, n_words, window);
+                             stream, in32, out, out_count, window);
         else
           hipLaunchKernelGGL((k_unpack_cast8<false, false>), g, dim3(kBlock),
-                             0, stream, in32, out, n_words, window);
+                             0, stream, in32, out, out_count, window);
       }
       break;
     }
@@ -395,6 +405,7 @@ hipError_t unpack(const uint8_t* in, float* out, size_t out_count, int nbits,
 hipError_t unpack_interleaved_2pol(const int8_t* in, float* out0, float* out1,
                                    size_t count_per_pol, const float* window,
                                    hipStream_t stream) {
+  if (count_per_pol % 4 != 0) return hipErrorInvalidValue;
   const size_t n_groups = count_per_pol / 4;
   const dim3 g = grid_for(n_groups);
   auto* in2 = reinterpret_cast<const uint2*>(in);
@@ -411,6 +422,7 @@ hipError_t unpack_interleaved_2pol(const int8_t* in, float* out0, float* out1,
 hipError_t unpack_naocpsr_snap1(const int8_t* in, float* out0, float* out1,
                                 size_t count_per_pol, const float* window,
                                 hipStream_t stream) {
+  if (count_per_pol % 4 != 0) return hipErrorInvalidValue;
   const size_t n_groups = count_per_pol / 4;
   const dim3 g = grid_for(n_groups);
   auto* in2 = reinterpret_cast<const uint2*>(in);
@@ -428,6 +440,7 @@ hipError_t unpack_gznupsr_a1(const uint8_t* in, float* out0, float* out1,
                              float* out2, float* out3, int n_streams,
                              size_t count_per_stream, const float* window,
                              hipStream_t stream) {
+  if (count_per_stream % 4 != 0) return hipErrorInvalidValue;
   const size_t n_groups = count_per_stream / 4;
   const dim3 g = grid_for(n_groups);
   auto* in32 = reinterpret_cast<const uint32_t*>(in);

@@ -139,7 +139,7 @@ def test_engine_subbyte_paths(C, bits):
     assert abs(int(np.argmax(ts)) - expect_bin) <= 2
 
 
-@pytest.mark.parametrize("bits", [2, -8, -16])
+@pytest.mark.parametrize("bits", [1, 2, 4, 8, -8, 16, -16])
 def test_engine_subbyte_fused_matches_unfused(C, monkeypatch, bits):
     """The fused decode-at-load path must produce the same time series as
     the standalone unpack kernel path (SRTB_NO_FUSED_UNPACK)."""
