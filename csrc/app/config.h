@@ -210,6 +210,9 @@ struct Config {
   size_t filterbank_fscrunch = 1;
   int filterbank_nbits = 8;
   double filterbank_tstart_mjd = 0.0;
+  // two-polarization formats: "" = one file per data stream; I, AABBCRCI or
+  // IQUV = one file of polarization products from both streams
+  std::string filterbank_polarization;
   // pulsar folding ("" = off), twin of the Python keys: period (s), its
   // derivative (s/s), phase bins, phase (turns) at stream sample 0, blocks
   // per sub-integration (0 = one for the whole run)
@@ -293,6 +296,12 @@ inline void Config::assign(const std::string& key, const std::string& raw0) {
   else if (key == "filterbank_fscrunch") filterbank_fscrunch = I();
   else if (key == "filterbank_nbits") filterbank_nbits = (int)Expr::eval_int(raw);
   else if (key == "filterbank_tstart_mjd") filterbank_tstart_mjd = D();
+  else if (key == "filterbank_polarization") {
+    if (!raw.empty() && raw != "I" && raw != "AABBCRCI" && raw != "IQUV")
+      throw std::runtime_error("filterbank_polarization: '" + raw +
+                               "' is not one of I, AABBCRCI, IQUV (or empty)");
+    filterbank_polarization = raw;
+  }
   else if (key == "fold_output_path") fold_output_path = raw;
   else if (key == "fold_period") fold_period = D();
   else if (key == "fold_period_derivative") fold_period_derivative = D();
@@ -382,6 +391,8 @@ inline std::string Config::dump() const {
       << "filterbank_tstart_mjd = " << filterbank_tstart_mjd << "\n";
     o.precision(prec);
   }
+  if (!filterbank_polarization.empty())
+    o << "filterbank_polarization = " << filterbank_polarization << "\n";
   if (!fold_output_path.empty()) {
     const auto prec = o.precision(17);
     o << "fold_output_path = " << fold_output_path << "\n"

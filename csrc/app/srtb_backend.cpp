@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../engine/engine.h"
+#include "../engine/pol_combiner.h"
 #include "comm.h"
 #include "config.h"
 #include "runtime.h"
@@ -217,6 +218,31 @@ int main(int argc, char** argv) {
   }
   const size_t fil_t = fil_mode ? cfg.filterbank_tscrunch : 1;
 
+  // polarization products (filterbank_polarization): the two per-polarization
+  // engines make no planes of their own, one PolCombiner joins them
+  const bool pol_mode = !cfg.filterbank_polarization.empty();
+  const int pol_state = cfg.filterbank_polarization == "I"
+                            ? srtb_hip::kPolStateI
+                            : cfg.filterbank_polarization == "AABBCRCI"
+                                  ? srtb_hip::kPolStateAABBCRCI
+                                  : srtb_hip::kPolStateIQUV;
+  if (pol_mode && !fil_mode) {
+    SRTB_APP_LOGE("config: filterbank_polarization needs "
+                  "filterbank_output_path");
+    return 2;
+  }
+  if (pol_mode && n_streams != 2) {
+    SRTB_APP_LOGE("config: filterbank_polarization needs a "
+                  "baseband_format_type with exactly two data streams ("
+                  << fmt_name << " has " << n_streams << ")");
+    return 2;
+  }
+  if (pol_mode && trial_mode) {
+    SRTB_APP_LOGE("config: filterbank_polarization and dm_trial_list exclude "
+                  "each other (a filterbank file holds one DM)");
+    return 2;
+  }
+
   // pulsar folding (fold_output_path): one DM per profile
   const bool fold_mode = !cfg.fold_output_path.empty();
   double fold_f0 = 0.0, fold_f1 = 0.0;
@@ -293,9 +319,11 @@ int main(int argc, char** argv) {
   ec.nsamps_reserved = reserved;
   ec.max_dm_trials = (int)trial_dms.size();
   if (fil_mode) {
-    ec.fil_tscrunch = cfg.filterbank_tscrunch;
-    ec.fil_fscrunch = cfg.filterbank_fscrunch;
-    ec.fil_nbits = cfg.filterbank_nbits;
+    if (!pol_mode) {
+      ec.fil_tscrunch = cfg.filterbank_tscrunch;
+      ec.fil_fscrunch = cfg.filterbank_fscrunch;
+      ec.fil_nbits = cfg.filterbank_nbits;
+    }
     const size_t per = 2 * cfg.spectrum_channel_count * fil_t;
     if (reserved >= cfg.baseband_input_count ||
         (cfg.baseband_input_count - reserved) % per != 0) {
@@ -347,6 +375,19 @@ int main(int argc, char** argv) {
   for (int i = 0; i < n_streams; ++i)
     engines.emplace_back(std::make_unique<PipelineEngine>(ec, 2));
   PipelineEngine& engine = *engines[0];
+  std::unique_ptr<srtb_hip::PolCombiner> combiner;
+  if (pol_mode) {
+    srtb_hip::PolCombinerConfig pc;
+    pc.baseband_input_count = cfg.baseband_input_count;
+    pc.spectrum_channel_count = cfg.spectrum_channel_count;
+    pc.nsamps_reserved = reserved;
+    pc.tscrunch = cfg.filterbank_tscrunch;
+    pc.fscrunch = cfg.filterbank_fscrunch;
+    pc.reverse = cfg.baseband_bandwidth > 0;
+    pc.pol_state = pol_state;
+    pc.nbits = cfg.filterbank_nbits;
+    combiner = std::make_unique<srtb_hip::PolCombiner>(pc, 2);
+  }
   const size_t n_per_pol = cfg.baseband_input_count;
   const size_t raw_bytes = (n_streams > 1)
                                ? n_per_pol * (size_t)n_streams
@@ -515,6 +556,7 @@ int main(int argc, char** argv) {
     std::array<int, 2> slots{-1, -1};
     int buf_index;
     uint64_t counter;
+    int pol_slot = -1;  // the combiner's slot (filterbank_polarization)
   };
   std::vector<InFlight> inflight;
   const size_t S = engine.n_channels(), Lw = engine.waterfall_len();
@@ -546,17 +588,23 @@ int main(int argc, char** argv) {
                                            << " valid bytes/block)");
   }
 
-  // filterbank output: one file per data stream, header written here, block
-  // rows appended by the pool as pwrite-at-offset (like baseband_write_all)
+  // filterbank output: one file per data stream (one in all with
+  // filterbank_polarization), header written here, block rows appended by the
+  // pool as pwrite-at-offset (like baseband_write_all)
   std::vector<int> fil_fds;
   size_t fil_header_len = 0, fil_block_bytes = 0;
   uint64_t fil_index = 0, fil_delta = 0;
   if (fil_mode) {
     FilterbankHeader fh;
     const double bw = std::fabs(cfg.baseband_bandwidth);
-    const size_t C = engine.filterbank_channels();
+    const size_t C = pol_mode ? combiner->channels()
+                              : engine.filterbank_channels();
+    const size_t fil_rows = pol_mode ? combiner->rows()
+                                     : engine.filterbank_rows();
+    const int fil_files = pol_mode ? 1 : n_streams;
     fh.nchans = (int)C;
     fh.nbits = cfg.filterbank_nbits;
+    if (pol_mode) fh.nifs = combiner->nifs();
     fh.foff = -bw / (double)C;
     fh.fch1 = std::max(cfg.baseband_freq_low,
                        cfg.baseband_freq_low + cfg.baseband_bandwidth) -
@@ -566,11 +614,11 @@ int main(int argc, char** argv) {
     fh.tstart = cfg.filterbank_tstart_mjd;
     const std::string header = filterbank_header(fh);
     fil_header_len = header.size();
-    fil_block_bytes = engine.filterbank_rows() * C *
+    fil_block_bytes = fil_rows * (size_t)fh.nifs * C *
                       (size_t)(cfg.filterbank_nbits / 8);
-    for (int si = 0; si < n_streams; ++si) {
+    for (int si = 0; si < fil_files; ++si) {
       std::string tag;
-      if (n_streams > 1) tag += "_s" + std::to_string(si);
+      if (fil_files > 1) tag += "_s" + std::to_string(si);
       if (comm.world() > 1) tag += "_r" + std::to_string(comm.rank());
       const std::string path =
           tag_before_extension(cfg.filterbank_output_path, tag);
@@ -582,8 +630,9 @@ int main(int argc, char** argv) {
         return 3;
       }
       fil_fds.push_back(fd);
-      SRTB_APP_LOGI("filterbank -> " << path << " (" << engine.filterbank_rows()
-                                     << " rows x " << C << " channels, "
+      SRTB_APP_LOGI("filterbank -> " << path << " (" << fil_rows << " rows x "
+                                     << fh.nifs << " ifs x " << C
+                                     << " channels, "
                                      << cfg.filterbank_nbits
                                      << " bits per block)");
     }
@@ -840,6 +889,9 @@ int main(int argc, char** argv) {
     } else {
       for (int si = 0; si < n_streams; ++si)
         res[si] = engines[si]->wait(w.slots[si]);
+      // the combiner read both slots in place: they are free for the next
+      // submission only once its plane is done
+      if (pol_mode) combiner->wait(w.pol_slot);
     }
     ++blocks;
     if (fil_mode) {
@@ -855,9 +907,10 @@ int main(int argc, char** argv) {
       }
       const uint64_t off =
           fil_header_len + fil_index++ * (uint64_t)fil_block_bytes;
-      for (int si = 0; si < n_streams; ++si) {
+      for (size_t si = 0; si < fil_fds.size(); ++si) {
         const uint8_t* src = static_cast<const uint8_t*>(
-            engines[si]->filterbank_host(w.slots[si]));
+            pol_mode ? combiner->host(w.pol_slot)
+                     : engines[si]->filterbank_host(w.slots[si]));
         auto rows = std::make_shared<std::vector<uint8_t>>(
             src, src + fil_block_bytes);
         const int fd = fil_fds[si];
@@ -977,8 +1030,12 @@ int main(int argc, char** argv) {
       while (!inflight.empty()) drain_one();
       fold_flush();
     }
-    inflight.push_back({submit_block(msg.buf_index, msg.counter),
-                        msg.buf_index, msg.counter});
+    InFlight blk{submit_block(msg.buf_index, msg.counter), msg.buf_index,
+                 msg.counter};
+    if (pol_mode)
+      blk.pol_slot = combiner->submit(*engines[0], blk.slots[0], *engines[1],
+                                      blk.slots[1]);
+    inflight.push_back(blk);
     if (inflight.size() >= 2) drain_one();
   }
   while (!inflight.empty()) drain_one();

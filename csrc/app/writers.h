@@ -87,10 +87,11 @@ inline void write_spectrum_npy(const std::string& prefix, uint64_t counter,
 
 // sigproc filterbank header, byte-identical to the Python twin
 // srtb_amd.io.writers.filterbank_header with its default telescope_id,
-// machine_id, data_type, nifs, source_name and coordinates.
+// machine_id, data_type, source_name and coordinates.
 struct FilterbankHeader {
   double fch1 = 0, foff = 0, tsamp = 0, tstart = 0;
   int nchans = 0, nbits = 32;
+  int nifs = 1;  // > 1: the data is [rows][nifs][nchans]
 };
 
 inline std::string filterbank_header(const FilterbankHeader& h) {
@@ -118,7 +119,7 @@ inline std::string filterbank_header(const FilterbankHeader& h) {
   put_real("tsamp", h.tsamp);
   put_real("tstart", h.tstart);
   put_int("nbits", h.nbits);
-  put_int("nifs", 1);
+  put_int("nifs", h.nifs);
   put_real("src_raj", 0.0);
   put_real("src_dej", 0.0);
   put_str("source_name");

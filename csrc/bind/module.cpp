@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../engine/engine.h"
+#include "../engine/pol_combiner.h"
 #include "../fft/native_fft.h"
 #include "../include/srtb_kernels.h"
 
@@ -501,6 +502,52 @@ torch::Tensor t_filterbank_detect(torch::Tensor wf,
   check(filterbank_detect(cptr(wf), f, S, L, valid_rows, tscrunch, fscrunch,
                           reverse, out.data_ptr<float>(), cur_stream()),
         "filterbank_detect");
+  return out;
+}
+
+// [R][P][C] float32 polarization products of two waterfalls of the same sky
+torch::Tensor t_filterbank_detect_pol(torch::Tensor wf_a, torch::Tensor wf_b,
+                                      c10::optional<torch::Tensor> flags_a,
+                                      c10::optional<torch::Tensor> flags_b,
+                                      int64_t valid_rows, int64_t tscrunch,
+                                      int64_t fscrunch, bool reverse,
+                                      int64_t pol_state) {
+  CHECK_CUDA(wf_a);
+  CHECK_CONTIG(wf_a);
+  CHECK_CUDA(wf_b);
+  CHECK_CONTIG(wf_b);
+  TORCH_CHECK(wf_a.dim() == 2 && wf_a.scalar_type() == torch::kComplexFloat &&
+                  wf_b.dim() == 2 && wf_b.scalar_type() == torch::kComplexFloat,
+              "filterbank_detect_pol: waterfalls must be 2-D complex64");
+  TORCH_CHECK(wf_a.sizes() == wf_b.sizes(),
+              "filterbank_detect_pol: the two waterfalls differ in shape");
+  const int64_t S = wf_a.size(0), L = wf_a.size(1);
+  const int P = pol_state_nifs((int)pol_state);
+  TORCH_CHECK(pol_state >= 0 && P > 0,
+              "filterbank_detect_pol: pol_state must be 0 (I), 1 (AABBCRCI) "
+              "or 2 (IQUV)");
+  TORCH_CHECK(tscrunch >= 1 && fscrunch >= 1 && S % fscrunch == 0 &&
+                  valid_rows >= tscrunch && valid_rows <= L && L % 2 == 0,
+              "filterbank_detect_pol: bad geometry");
+  auto flag_ptr = [&](const c10::optional<torch::Tensor>& flags) {
+    const uint8_t* f = nullptr;
+    if (flags.has_value()) {
+      CHECK_CUDA(*flags);
+      CHECK_CONTIG(*flags);
+      TORCH_CHECK(flags->scalar_type() == torch::kUInt8 &&
+                  flags->numel() == S);
+      f = flags->data_ptr<uint8_t>();
+    }
+    return f;
+  };
+  const uint8_t* fa = flag_ptr(flags_a);
+  const uint8_t* fb = flag_ptr(flags_b);
+  auto out = torch::empty({valid_rows / tscrunch, (int64_t)P, S / fscrunch},
+                          wf_a.options().dtype(torch::kFloat32));
+  check(filterbank_detect_pol(cptr(wf_a), cptr(wf_b), fa, fb, S, L, valid_rows,
+                              tscrunch, fscrunch, reverse, (int)pol_state,
+                              out.data_ptr<float>(), cur_stream()),
+        "filterbank_detect_pol");
   return out;
 }
 
@@ -1173,6 +1220,8 @@ class PyEngine {
   int64_t filterbank_rows() const { return eng_->filterbank_rows(); }
   int64_t filterbank_channels() const { return eng_->filterbank_channels(); }
 
+  PipelineEngine& engine() { return *eng_; }
+
   int64_t n() const { return eng_->n(); }
   int64_t nc() const { return eng_->nc(); }
   int64_t n_channels() const { return eng_->n_channels(); }
@@ -1189,6 +1238,74 @@ class PyEngine {
   ~PyEngine() {
     if (prod_ev_) (void)hipEventDestroy(prod_ev_);
   }
+};
+
+// ---------------- polarization combiner binding ----------------
+
+class PyPolCombiner {
+ public:
+  PyPolCombiner(int64_t n, int64_t channels, int64_t nsamps_reserved,
+                int64_t tscrunch, int64_t fscrunch, bool reverse,
+                int64_t pol_state, int64_t nbits, int64_t n_slots) {
+    TORCH_CHECK(n >= 0 && channels >= 0 && nsamps_reserved >= 0 &&
+                    tscrunch >= 0 && fscrunch >= 0,
+                "PolCombiner: sizes must not be negative");
+    PolCombinerConfig c;
+    c.baseband_input_count = (size_t)n;
+    c.spectrum_channel_count = (size_t)channels;
+    c.nsamps_reserved = (size_t)nsamps_reserved;
+    c.tscrunch = (size_t)tscrunch;
+    c.fscrunch = (size_t)fscrunch;
+    c.reverse = reverse;
+    c.pol_state = (int)pol_state;
+    c.nbits = (int)nbits;
+    comb_ = std::make_unique<PolCombiner>(c, (int)n_slots);
+  }
+
+  int64_t submit(PyEngine& a, int64_t slot_a, PyEngine& b, int64_t slot_b) {
+    return comb_->submit(a.engine(), (int)slot_a, b.engine(), (int)slot_b);
+  }
+
+  void wait(int64_t k) { comb_->wait((int)k); }
+
+  std::vector<int64_t> shape() const {
+    return {(int64_t)comb_->rows(), (int64_t)comb_->nifs(),
+            (int64_t)comb_->channels()};
+  }
+
+  // [R][P][C] uint8 or float32: a copy of the slot's pinned mirror, complete
+  // after wait(k)
+  torch::Tensor plane(int64_t k) {
+    const auto dt = comb_->nbits() == 8 ? torch::kUInt8 : torch::kFloat32;
+    return torch::from_blob(const_cast<void*>(comb_->host((int)k)), shape(),
+                            torch::TensorOptions().dtype(dt))
+        .clone();
+  }
+
+  torch::Tensor power(int64_t k) {
+    return torch::from_blob(comb_->power_ptr((int)k), shape(),
+                            torch::TensorOptions()
+                                .dtype(torch::kFloat32)
+                                .device(torch::kCUDA));
+  }
+
+  // (mean, std) per (product, channel), CPU float32 [P * C] (8-bit only)
+  std::vector<torch::Tensor> stats(int64_t k) {
+    const auto pc = (int64_t)comb_->nifs() * (int64_t)comb_->channels();
+    auto opt = torch::TensorOptions().dtype(torch::kFloat32);
+    auto mean = torch::from_blob(
+        const_cast<float*>(comb_->mean_host((int)k)), {pc}, opt);
+    auto stddev = torch::from_blob(
+        const_cast<float*>(comb_->std_host((int)k)), {pc}, opt);
+    return {mean.clone(), stddev.clone()};
+  }
+
+  int64_t rows() const { return comb_->rows(); }
+  int64_t channels() const { return comb_->channels(); }
+  int64_t nifs() const { return comb_->nifs(); }
+
+ private:
+  std::unique_ptr<PolCombiner> comb_;
 };
 
 }  // namespace
@@ -1236,6 +1353,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("filterbank_detect", &t_filterbank_detect, py::arg("wf"),
         py::arg("flags"), py::arg("valid_rows"), py::arg("tscrunch"),
         py::arg("fscrunch"), py::arg("reverse"));
+  m.def("filterbank_detect_pol", &t_filterbank_detect_pol, py::arg("wf_a"),
+        py::arg("wf_b"), py::arg("flags_a"), py::arg("flags_b"),
+        py::arg("valid_rows"), py::arg("tscrunch"), py::arg("fscrunch"),
+        py::arg("reverse"), py::arg("pol_state"));
   m.def("filterbank_channel_stats", &t_filterbank_channel_stats, py::arg("P"));
   m.def("filterbank_quantize", &t_filterbank_quantize, py::arg("P"),
         py::arg("mean"), py::arg("std"));
@@ -1319,4 +1440,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property_readonly("ts_count", &PyEngine::ts_count)
       .def_property_readonly("raw_bytes", &PyEngine::raw_bytes)
       .def_property_readonly("n_slots", &PyEngine::n_slots);
+
+  py::class_<PyPolCombiner>(m, "PolCombiner")
+      .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, bool,
+                    int64_t, int64_t, int64_t>(),
+           py::arg("n"), py::arg("channels"), py::arg("nsamps_reserved") = 0,
+           py::arg("tscrunch") = 16, py::arg("fscrunch") = 1,
+           py::arg("reverse") = false, py::arg("pol_state") = 2,
+           py::arg("nbits") = 32, py::arg("n_slots") = 2)
+      .def("submit", &PyPolCombiner::submit, py::arg("eng_a"),
+           py::arg("slot_a"), py::arg("eng_b"), py::arg("slot_b"))
+      .def("wait", &PyPolCombiner::wait)
+      .def("plane", &PyPolCombiner::plane)
+      .def("power", &PyPolCombiner::power)
+      .def("stats", &PyPolCombiner::stats)
+      .def_property_readonly("rows", &PyPolCombiner::rows)
+      .def_property_readonly("channels", &PyPolCombiner::channels)
+      .def_property_readonly("nifs", &PyPolCombiner::nifs);
 }

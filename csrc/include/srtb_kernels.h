@@ -238,6 +238,29 @@ hipError_t filterbank_detect(const float2* wf, const uint8_t* flags, size_t S,
                              size_t fscrunch, bool reverse, float* out,
                              hipStream_t stream);
 
+// Polarization products of two waterfalls of the same sky (definition:
+// docs/ARCHITECTURE.md, "Polarization products").  With A = x+iy = wf_a and
+// B = u+iv = wf_b at the same row and column: AA = x^2+y^2, BB = u^2+v^2,
+// CR = xu+yv, CI = yu-xv, each summed over the cell exactly as
+// filterbank_detect sums its power.  out[r][p][c] ([R][P][C], c fastest):
+// pol_state I -> P = 1: AA+BB; AABBCRCI -> P = 4: AA, BB, CR, CI; IQUV ->
+// P = 4: AA+BB, AA-BB, 2CR, 2CI, formed from the four fp32 cell sums.  A row
+// flagged in either flags_a or flags_b contributes 0 to every product; either
+// pointer may be null.  wf_a, wf_b: [S][L] each, 16-byte aligned; out:
+// R * P * C floats; flags: [S] bytes.  One pass, no atomics, bit-identical
+// from run to run.  Geometry rules of filterbank_detect; anything else, or a
+// pol_state outside the three, returns hipErrorInvalidValue.
+constexpr int kPolStateI = 0;
+constexpr int kPolStateAABBCRCI = 1;
+constexpr int kPolStateIQUV = 2;
+int pol_state_nifs(int pol_state);  // P: 1 or 4; 0 = not a state
+hipError_t filterbank_detect_pol(const float2* wf_a, const float2* wf_b,
+                                 const uint8_t* flags_a,
+                                 const uint8_t* flags_b, size_t S, size_t L,
+                                 size_t V, size_t tscrunch, size_t fscrunch,
+                                 bool reverse, int pol_state, float* out,
+                                 hipStream_t stream);
+
 // Per-channel mean and (population) standard deviation of P[R][C], two-stage
 // with fp64 partials combined in fixed order, stored as float.  partials:
 // device scratch of filterbank_stats_partials(C) doubles.

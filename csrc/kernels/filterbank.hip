@@ -122,6 +122,154 @@ k_filterbank_detect(const float2* __restrict__ wf,
   }
 }
 
+// ---- polarization products (docs/ARCHITECTURE.md, "Polarization products")
+// Two waterfalls A = x+iy, B = u+iv of the same sky -> AA, BB, CR, CI per cell.
+// NA = 1 keeps only AA+BB (state I), NA = 4 keeps all four; v holds two
+// complex samples of each waterfall.
+template <int NA>
+__device__ __forceinline__ void pol_acc2(float (&acc)[NA], float4 a,
+                                         float4 b) {
+  if constexpr (NA == 1) {
+    acc[0] += power4(a) + power4(b);
+  } else {
+    acc[0] += power4(a);
+    acc[1] += power4(b);
+    acc[2] += (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
+    acc[3] += (a.y * b.x - a.x * b.y) + (a.w * b.z - a.z * b.w);
+  }
+}
+
+// one complex sample of each (the tscrunch = 1 path)
+template <int NA>
+__device__ __forceinline__ void pol_acc1(float (&acc)[NA], float x, float y,
+                                         float u, float v) {
+  if constexpr (NA == 1) {
+    acc[0] += (x * x + y * y) + (u * u + v * v);
+  } else {
+    acc[0] += x * x + y * y;
+    acc[1] += u * u + v * v;
+    acc[2] += x * u + y * v;
+    acc[3] += y * u - x * v;
+  }
+}
+
+// k_filterbank_detect's tiling with NA accumulators per cell and an
+// [NA][rows][33] LDS tile; out is [R][NA][C].  iquv (NA = 4 only): the four
+// cell sums leave as I, Q, U, V, one fp32 operation each.  The tile is dynamic
+// LDS sized by the launcher: 64 rows are needed only by the tscrunch = 1 path,
+// and with 32 the four-product tile is 16.5 KB instead of 33 KB, which is what
+// lets eight workgroups instead of four share a CU.
+template <int NA>
+__global__ void __launch_bounds__(kBlock)
+k_filterbank_detect_pol(const float2* __restrict__ wa,
+                        const float2* __restrict__ wb,
+                        const uint8_t* __restrict__ fa,
+                        const uint8_t* __restrict__ fb, size_t S, size_t L,
+                        size_t V, unsigned q4, unsigned G, unsigned fscrunch,
+                        int reverse, int iquv, size_t R, size_t C,
+                        unsigned tiles_r, float* __restrict__ out) {
+  extern __shared__ float pol_tile[];
+  const unsigned rows_here = q4 == 0 ? kFilTileRows : kFilTileR;
+  // tile[p][rl][cl]
+  auto tile = [&](unsigned p, unsigned rl, unsigned cl) -> float& {
+    return pol_tile[(p * rows_here + rl) * (kFilTileC + 1) + cl];
+  };
+  const unsigned tile_r = blockIdx.x % tiles_r;
+  const unsigned tile_c = blockIdx.x / tiles_r;
+  const size_t c0 = (size_t)tile_c * kFilTileC;
+  const unsigned tid = threadIdx.x;
+
+  if (q4 == 0) {
+    // tscrunch = 1: cell = one float4 column of one channel, two output rows
+    const size_t r0 = (size_t)tile_r * kFilTileRows;
+#pragma unroll
+    for (unsigned it = 0; it < kFilTileC * kFilTileR / kBlock; ++it) {
+      const unsigned o = tid + it * kBlock;
+      const unsigned j = o % kFilTileR, cl = o / kFilTileR;
+      const size_t c = c0 + cl, r = r0 + 2 * (size_t)j;
+      float a0[NA] = {}, a1[NA] = {};
+      if (c < C && r < R) {
+        const size_t row0 = reverse ? S - (c + 1) * fscrunch : c * fscrunch;
+        for (unsigned f = 0; f < fscrunch; ++f) {
+          const size_t row = row0 + f;
+          if ((fa && fa[row]) || (fb && fb[row])) continue;
+          // r is even and r < V <= L with L even: the float4 stays in the row
+          const float4 a = *reinterpret_cast<const float4*>(wa + row * L + r);
+          const float4 b = *reinterpret_cast<const float4*>(wb + row * L + r);
+          pol_acc1<NA>(a0, a.x, a.y, b.x, b.y);
+          pol_acc1<NA>(a1, a.z, a.w, b.z, b.w);
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < NA; ++p) {
+        tile(p, 2 * j, cl) = a0[p];
+        tile(p, 2 * j + 1, cl) = a1[p];
+      }
+    }
+  } else {
+    const size_t r0 = (size_t)tile_r * kFilTileR;
+    const unsigned g = tid % G;           // lane within the cell's group
+    const unsigned per_it = kBlock / G;   // cells per iteration
+    const unsigned n_it = kFilTileC * kFilTileR / per_it;
+    const unsigned n_i = q4 / G;          // float4 per lane, row and cell
+    for (unsigned it = 0; it < n_it; ++it) {
+      const unsigned o = tid / G + it * per_it;
+      const unsigned rl = o % kFilTileR, cl = o / kFilTileR;
+      const size_t c = c0 + cl, r = r0 + rl;
+      float acc[NA] = {};
+      if (c < C && r < R) {
+        const size_t row0 = reverse ? S - (c + 1) * fscrunch : c * fscrunch;
+        // (r + 1) * tscrunch <= V <= L: every float4 stays in the row
+        const size_t t4 = r * q4 + g;
+        for (unsigned f = 0; f < fscrunch; ++f) {
+          const size_t row = row0 + f;
+          if ((fa && fa[row]) || (fb && fb[row])) continue;
+          const float4* pa =
+              reinterpret_cast<const float4*>(wa + row * L) + t4;
+          const float4* pb =
+              reinterpret_cast<const float4*>(wb + row * L) + t4;
+          for (unsigned i = 0; i < n_i; ++i)
+            pol_acc2<NA>(acc, pa[(size_t)i * G], pb[(size_t)i * G]);
+        }
+      }
+      // fold the cell's G lanes (all lanes take part: uniform trip counts)
+      for (unsigned off = G >> 1; off > 0; off >>= 1) {
+#pragma unroll
+        for (int p = 0; p < NA; ++p)
+          acc[p] += __shfl_xor(acc[p], (int)off, 64);
+      }
+      if (g == 0) {
+#pragma unroll
+        for (int p = 0; p < NA; ++p) tile(p, rl, cl) = acc[p];
+      }
+    }
+  }
+  __syncthreads();
+
+  // read-out along the channel axis, one run of C per product
+  const size_t rbase = (size_t)tile_r * rows_here;
+  const unsigned cl = tid % kFilTileC;
+  const size_t c = c0 + cl;
+  if (c < C) {
+    for (unsigned rl = tid / kFilTileC; rl < rows_here;
+         rl += kBlock / kFilTileC) {
+      const size_t r = rbase + rl;
+      if (r >= R) continue;
+      float* o = out + r * NA * C + c;
+      if constexpr (NA == 1) {
+        o[0] = tile(0, rl, cl);
+      } else {
+        const float aa = tile(0, rl, cl), bb = tile(1, rl, cl);
+        const float cr = tile(2, rl, cl), ci = tile(3, rl, cl);
+        o[0] = iquv ? aa + bb : aa;
+        o[C] = iquv ? aa - bb : bb;
+        o[2 * C] = iquv ? cr + cr : cr;
+        o[3 * C] = iquv ? ci + ci : ci;
+      }
+    }
+  }
+}
+
 // Stage 1: sums of d = P[r][c] - P[0][c] and of d^2 over the rows of chunk
 // blockIdx.y; one thread per channel, so loads run along c.  The shift by the
 // channel's first sample keeps a constant channel at exactly zero variance.
@@ -224,6 +372,48 @@ hipError_t filterbank_detect(const float2* wf, const uint8_t* flags, size_t S,
                      dim3(kBlock), 0, stream, wf, flags, S, L, V, q4, G,
                      (unsigned)fscrunch, reverse ? 1 : 0, R, C,
                      (unsigned)tiles_r, out);
+  SRTB_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+int pol_state_nifs(int pol_state) {
+  if (pol_state == kPolStateI) return 1;
+  if (pol_state == kPolStateAABBCRCI || pol_state == kPolStateIQUV) return 4;
+  return 0;
+}
+
+hipError_t filterbank_detect_pol(const float2* wf_a, const float2* wf_b,
+                                 const uint8_t* flags_a,
+                                 const uint8_t* flags_b, size_t S, size_t L,
+                                 size_t V, size_t tscrunch, size_t fscrunch,
+                                 bool reverse, int pol_state, float* out,
+                                 hipStream_t stream) {
+  if (!is_pow2(tscrunch) || tscrunch > kFilterbankMaxTscrunch ||
+      fscrunch == 0 || S % fscrunch != 0 || V > L || V < tscrunch ||
+      L % 2 != 0 || pol_state_nifs(pol_state) == 0)
+    return hipErrorInvalidValue;
+  const size_t R = V / tscrunch, C = S / fscrunch;
+  const unsigned q4 = (unsigned)(tscrunch / 2);
+  const unsigned G = q4 > 64 ? 64u : q4;
+  const size_t rows_per_tile = q4 == 0 ? kFilTileRows : kFilTileR;
+  const size_t tiles_r = (R + rows_per_tile - 1) / rows_per_tile;
+  const size_t tiles_c = (C + kFilTileC - 1) / kFilTileC;
+  if (tiles_r * tiles_c >= (1ull << 31)) return hipErrorInvalidValue;
+  const dim3 grid((uint32_t)(tiles_r * tiles_c));
+  // [P][rows_per_tile][33] floats
+  const size_t lds = (size_t)pol_state_nifs(pol_state) * rows_per_tile *
+                     (kFilTileC + 1) * sizeof(float);
+  if (pol_state == kPolStateI)
+    hipLaunchKernelGGL(k_filterbank_detect_pol<1>, grid, dim3(kBlock), lds,
+                       stream, wf_a, wf_b, flags_a, flags_b, S, L, V, q4, G,
+                       (unsigned)fscrunch, reverse ? 1 : 0, 0, R, C,
+                       (unsigned)tiles_r, out);
+  else
+    hipLaunchKernelGGL(k_filterbank_detect_pol<4>, grid, dim3(kBlock), lds,
+                       stream, wf_a, wf_b, flags_a, flags_b, S, L, V, q4, G,
+                       (unsigned)fscrunch, reverse ? 1 : 0,
+                       pol_state == kPolStateIQUV ? 1 : 0, R, C,
+                       (unsigned)tiles_r, out);
   SRTB_CHECK_LAUNCH();
   return hipSuccess;
 }

@@ -2,7 +2,7 @@
 
 Two stages:
   1. hipcc --offload-arch=gfx950 compiles the pure-HIP kernel/engine TUs
-     (csrc/kernels/*.hip, csrc/engine/engine.cpp) — no torch headers, fast.
+     (csrc/kernels/*.hip, csrc/engine/*.cpp) — no torch headers, fast.
   2. the torch extension TU (csrc/bind/module.cpp) is built by
      torch.utils.cpp_extension and linked against the stage-1 objects and
      hipfft.
@@ -31,6 +31,7 @@ HIP_SOURCES = [
     "csrc/kernels/filterbank.hip",
     "csrc/kernels/fold.hip",
     "csrc/engine/engine.cpp",
+    "csrc/engine/pol_combiner.cpp",
 ]
 
 HIPCC_FLAGS = [
@@ -53,6 +54,7 @@ def build_hip_objects():
                 os.path.join(ROOT, "csrc/include/srtb_kernels.h"),
                 os.path.join(ROOT, "csrc/kernels/common.h"),
                 os.path.join(ROOT, "csrc/engine/engine.h"),
+                os.path.join(ROOT, "csrc/engine/pol_combiner.h"),
                 os.path.join(ROOT, "csrc/fft/fft_plans.h"),
                 os.path.join(ROOT, "csrc/fft/native_fft.h")]
         if os.path.exists(obj) and all(
@@ -86,7 +88,8 @@ def build_apps(objects):
                 "csrc/app/config.h", "csrc/app/runtime.h", "csrc/app/comm.h",
                 "csrc/app/pipe.h",
                 "csrc/app/udp_receiver.h", "csrc/app/writers.h",
-                "csrc/engine/engine.h", "csrc/fft/native_fft.h")]
+                "csrc/engine/engine.h", "csrc/engine/pol_combiner.h",
+                "csrc/fft/native_fft.h")]
         if os.path.exists(out) and all(
                 os.path.getmtime(out) >= os.path.getmtime(d) for d in deps
                 if os.path.exists(d)):

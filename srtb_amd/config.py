@@ -60,6 +60,7 @@ _FIELD_KINDS = {
     "filterbank_fscrunch": "int",
     "filterbank_nbits": "int",
     "filterbank_tstart_mjd": "real",
+    "filterbank_polarization": "polstate",
     "fold_output_path": "str",
     "fold_period": "real",
     "fold_period_derivative": "real",
@@ -67,6 +68,10 @@ _FIELD_KINDS = {
     "fold_phase_offset": "real",
     "fold_subint_blocks": "int",
 }
+
+
+# values of filterbank_polarization ("" = off); the names of ref.POL_STATES
+FILTERBANK_POLARIZATIONS = ("", "I", "AABBCRCI", "IQUV")
 
 
 @dataclass
@@ -113,6 +118,9 @@ class Config:
     filterbank_fscrunch: int = 1
     filterbank_nbits: int = 8
     filterbank_tstart_mjd: float = 0.0
+    # two-polarization formats: "" = one file per data stream; I, AABBCRCI or
+    # IQUV = one file of polarization products from both streams (nifs = 1 / 4)
+    filterbank_polarization: str = ""
     # pulsar folding: "" = off; spin period (s) and its derivative (s/s), phase
     # bins, phase (turns) at stream sample 0, blocks per sub-integration
     # (0 = one sub-integration for the whole run)
@@ -144,6 +152,12 @@ class Config:
             value = [evaluate_int(s) for s in raw.split(",") if s.strip()]
         elif kind == "reallist":
             _parse_real_list(raw)  # a malformed list is rejected here
+            value = raw
+        elif kind == "polstate":
+            if raw not in FILTERBANK_POLARIZATIONS:
+                raise ValueError(
+                    f"{key}: {raw!r} is not one of "
+                    f"{', '.join(FILTERBANK_POLARIZATIONS[1:])} (or empty)")
             value = raw
         else:  # pragma: no cover
             raise AssertionError(kind)

@@ -231,7 +231,9 @@ def write_filterbank(path: str, header: bytes, data: np.ndarray) -> None:
 class FilterbankWriter:
     """Continuous sigproc .fil stream: the header is written once, then
     blocks of [rows][nchans] samples (uint8 for nbits = 8, float32 for
-    nbits = 32) are appended in call order.
+    nbits = 32) are appended in call order.  With ``nifs`` > 1 in the header
+    keywords a block is [rows][nifs][nchans] (sigproc's order: channel
+    fastest, then IF).
 
     header_kwargs: the keyword arguments of :func:`filterbank_header`."""
 
@@ -239,8 +241,11 @@ class FilterbankWriter:
         self.path = path
         self.nchans = int(header_kwargs["nchans"])
         self.nbits = int(header_kwargs.get("nbits", 32))
+        self.nifs = int(header_kwargs.get("nifs", 1))
         if self.nbits not in (8, 32):
             raise ValueError("FilterbankWriter: nbits must be 8 or 32")
+        if self.nifs < 1:
+            raise ValueError("FilterbankWriter: nifs must be at least 1")
         self.dtype = np.uint8 if self.nbits == 8 else np.float32
         self.rows = 0
         self._f = open(path, "wb")
@@ -248,7 +253,12 @@ class FilterbankWriter:
 
     def append(self, block: np.ndarray) -> None:
         block = np.asarray(block)
-        if block.ndim != 2 or block.shape[1] != self.nchans:
+        if self.nifs > 1:
+            if block.ndim != 3 or block.shape[1:] != (self.nifs, self.nchans):
+                raise ValueError(
+                    f"FilterbankWriter: block shape {block.shape}, expected "
+                    f"[rows][{self.nifs}][{self.nchans}]")
+        elif block.ndim != 2 or block.shape[1] != self.nchans:
             raise ValueError(
                 f"FilterbankWriter: block shape {block.shape}, expected "
                 f"[rows][{self.nchans}]")
@@ -281,7 +291,8 @@ _HEADER_STR_KEYS = {"source_name", "rawdatafile"}
 def read_filterbank(path: str) -> tuple[dict, np.ndarray]:
     """Read a sigproc .fil file written with nbits 8 or 32.  Returns the
     header as a dict (plus ``header_len``, its size in bytes) and the data as
-    a [rows][nchans] uint8 or float32 array."""
+    a [rows][nchans] uint8 or float32 array, or [rows][nifs][nchans] when the
+    header says nifs > 1."""
     with open(path, "rb") as f:
         buf = f.read()
     pos = 0
@@ -317,6 +328,13 @@ def read_filterbank(path: str) -> tuple[dict, np.ndarray]:
         raise ValueError(f"{path}: nbits = {nbits} is not supported")
     dtype = np.uint8 if nbits == 8 else np.float32
     nchans = header["nchans"]
+    nifs = header.get("nifs", 1)
+    if nifs > 1:
+        per_row = nifs * nchans
+        rows = (len(buf) - pos) // (np.dtype(dtype).itemsize * per_row)
+        data = np.frombuffer(buf, dtype=dtype, offset=pos,
+                             count=rows * per_row)
+        return header, data.reshape(rows, nifs, nchans).copy()
     rows = (len(buf) - pos) // (np.dtype(dtype).itemsize * nchans)
     data = np.frombuffer(buf, dtype=dtype, offset=pos, count=rows * nchans)
     return header, data.reshape(rows, nchans).copy()

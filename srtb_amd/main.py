@@ -70,6 +70,9 @@ def filterbank_paths(cfg: Config, n_streams: int, rank: int, world: int,
     tag = f"_r{rank}" if world > 1 else ""
     if endpoint is not None:
         tag += f"_e{endpoint}"
+    if cfg.filterbank_polarization:
+        # one file of polarization products from both streams: no ``_s{k}``
+        return [stem + tag + ext]
     return [stem + (f"_s{k}" if n_streams > 1 else "") + tag + ext
             for k in range(n_streams)]
 
@@ -80,7 +83,47 @@ def filterbank_header_kwargs(cfg: Config) -> dict:
         cfg.baseband_sample_rate, cfg.spectrum_channel_count,
         cfg.filterbank_tscrunch, cfg.filterbank_fscrunch)
     kw.update(nbits=cfg.filterbank_nbits, tstart=cfg.filterbank_tstart_mjd)
+    if cfg.filterbank_polarization:
+        kw.update(nifs=ref.POL_STATE_NIFS[cfg.filterbank_polarization])
     return kw
+
+
+def check_filterbank_polarization(cfg: Config, n_streams: int) -> None:
+    """Reject a filterbank_polarization the run cannot honour."""
+    if not cfg.filterbank_polarization:
+        return
+    if not cfg.filterbank_output_path:
+        raise SystemExit(
+            "config: filterbank_polarization needs filterbank_output_path")
+    if n_streams != 2:
+        raise SystemExit(
+            "config: filterbank_polarization needs a baseband_format_type "
+            f"with exactly two data streams ({cfg.baseband_format_type!r} "
+            f"has {n_streams})")
+    if cfg.dm_trial_list.strip():
+        raise SystemExit(
+            "config: filterbank_polarization and dm_trial_list exclude each "
+            "other (a filterbank file holds one DM)")
+
+
+def cpu_pol_filterbank_block(cfg: Config, results: list,
+                             nsamps_reserved: int) -> np.ndarray:
+    """The combiner's [R][P][C] rows of one block from the oracle functions
+    (results: the two polarizations' CPU pipeline result dicts)."""
+    wf_a, wf_b = results[0]["waterfall"], results[1]["waterfall"]
+    valid = ref.filterbank_valid_rows(cfg.baseband_input_count, wf_a.shape[0],
+                                      nsamps_reserved)
+    plane = ref.pol_products_block(
+        wf_a, wf_b, valid, cfg.filterbank_tscrunch, cfg.filterbank_fscrunch,
+        reverse=cfg.baseband_bandwidth > 0,
+        pol_state=cfg.filterbank_polarization,
+        flags_a=results[0]["sk_flags"],
+        flags_b=results[1]["sk_flags"]).astype(np.float32)
+    if cfg.filterbank_nbits == 32:
+        return plane
+    flat = plane.reshape(plane.shape[0], -1)
+    mean, std = ref.filterbank_channel_stats(flat)
+    return ref.filterbank_quantize(flat, mean, std).reshape(plane.shape)
 
 
 def cpu_filterbank_block(cfg: Config, wf: np.ndarray,
@@ -304,6 +347,20 @@ class GpuMultiPolPipeline:
                                      **filterbank_engine_kwargs(cfg),
                                      **fold_engine_kwargs(cfg))
                         for _ in range(self.n_streams)]
+        # filterbank_polarization: the engines make no per-stream planes (the
+        # keywords above are empty then); one combiner joins the two streams
+        self.combiner = None
+        self.combiner_slot = None
+        if cfg.filterbank_polarization:
+            self.combiner = self.C.PolCombiner(
+                n=cfg.baseband_input_count,
+                channels=cfg.spectrum_channel_count,
+                nsamps_reserved=nsamps_reserved,
+                tscrunch=cfg.filterbank_tscrunch,
+                fscrunch=cfg.filterbank_fscrunch,
+                reverse=cfg.baseband_bandwidth > 0,
+                pol_state=ref.POL_STATES[cfg.filterbank_polarization],
+                nbits=cfg.filterbank_nbits)
 
     def fold_position(self, n0: int) -> None:
         for e in self.engines:
@@ -313,6 +370,10 @@ class GpuMultiPolPipeline:
         return _engine_fold_take(self.engines)
 
     def filterbank_blocks(self) -> list[np.ndarray]:
+        if self.combiner is not None:
+            k, self.combiner_slot = self.combiner_slot, None
+            self.combiner.wait(k)
+            return [self.combiner.plane(k).numpy()]
         return [e.filterbank(s).numpy()
                 for e, s in zip(self.engines, self.last_slots)]
 
@@ -326,8 +387,15 @@ class GpuMultiPolPipeline:
         torch = self.torch
         raw_t = torch.from_numpy(np.ascontiguousarray(raw)).cuda()
         pols = self._fanout(raw_t)
+        if self.combiner_slot is not None:
+            # the last plane was never fetched: the combiner still reads the
+            # engines' slots until its wait returns
+            self.combiner.wait(self.combiner_slot)
         slots = [eng.submit_samples(pol)
                  for eng, pol in zip(self.engines, pols)]
+        if self.combiner is not None:
+            self.combiner_slot = self.combiner.submit(
+                self.engines[0], slots[0], self.engines[1], slots[1])
         out = []
         results = []
         for eng, slot in zip(self.engines, slots):
@@ -390,6 +458,9 @@ class CpuMultiPolPipeline:
         return _cpu_fold_take(self.folders)
 
     def filterbank_blocks(self) -> list[np.ndarray]:
+        if self.cfg.filterbank_polarization:
+            return [cpu_pol_filterbank_block(self.cfg, self.last_results,
+                                             self.nsamps_reserved)]
         return [cpu_filterbank_block(self.cfg, r["waterfall"],
                                      self.nsamps_reserved)
                 for r in self.last_results]
@@ -537,6 +608,9 @@ def main(argv=None) -> int:
                 "filterbank_fscrunch a power of two dividing "
                 "spectrum_channel_count, filterbank_nbits 8 or 32")
 
+    check_filterbank_polarization(
+        cfg, bk.get_data_stream_count(cfg.baseband_format_type))
+
     fold_on = bool(cfg.fold_output_path)
     if fold_on:
         check_fold_config(cfg)
@@ -617,6 +691,8 @@ def main(argv=None) -> int:
             fil_writers[ep] = [FilterbankWriter(
                 p_, filterbank_header_kwargs(cfg)) for p_ in paths]
         for w, rows in zip(fil_writers[ep], pipe.filterbank_blocks()):
+            if rows.ndim == 3 and w.nifs == 1:
+                rows = rows[:, 0, :]  # polarization state I: [R][1][C]
             w.append(rows)
 
     if cfg.filterbank_output_path:

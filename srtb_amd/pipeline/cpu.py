@@ -81,7 +81,9 @@ class CpuPipeline:
             # (reference fft_pipe.hpp:350-358; rectangle default skips it)
             coef = ref.window_coefficients(self.window_kind, wf.shape[1])
             wf = wf / coef[None, :]
-        wf = ref.rfi_mitigate_sk(wf, c.mitigate_rfi_spectral_kurtosis_threshold)
+        flags = ref.sk_flags(wf, c.mitigate_rfi_spectral_kurtosis_threshold)
+        wf = np.asarray(wf).copy()
+        wf[flags, :] = 0
 
         det = ref.detect_signals(
             wf, self.nsamps_reserved(), c.signal_detect_signal_noise_threshold,
@@ -89,6 +91,7 @@ class CpuPipeline:
         return {
             "spectrum": spec,
             "waterfall": wf,
+            "sk_flags": flags,
             "time_series": det["time_series"],
             "zero_count": det["zero_count"],
             "detections": det["detections"],

@@ -293,11 +293,11 @@ def spectral_kurtosis_sk(wf: np.ndarray) -> np.ndarray:
     return sk
 
 
-def rfi_mitigate_sk(wf: np.ndarray, sk_threshold: float) -> np.ndarray:
-    """Method 2: zero whole frequency rows whose SK is outside the corrected
+def sk_flags(wf: np.ndarray, sk_threshold: float) -> np.ndarray:
+    """Boolean [n_channels]: rows whose SK is outside the corrected
     [lo', hi'] band; lo = 2 - thr, hi = thr, x' = x*(M-1)/(M+1) + 1
     (reference rfi_mitigation.hpp:292-340)."""
-    wf = np.asarray(wf).copy()
+    wf = np.asarray(wf)
     M = wf.shape[1]
     hi = float(sk_threshold)
     lo = 2.0 - hi
@@ -306,8 +306,13 @@ def rfi_mitigate_sk(wf: np.ndarray, sk_threshold: float) -> np.ndarray:
     corr = (M - 1.0) / (M + 1.0)
     lo_, hi_ = lo * corr + 1.0, hi * corr + 1.0
     sk = spectral_kurtosis_sk(wf)
-    zap = (sk > hi_) | (sk < lo_)
-    wf[zap, :] = 0
+    return (sk > hi_) | (sk < lo_)
+
+
+def rfi_mitigate_sk(wf: np.ndarray, sk_threshold: float) -> np.ndarray:
+    """Method 2: zero whole frequency rows that sk_flags() marks."""
+    wf = np.asarray(wf).copy()
+    wf[sk_flags(wf, sk_threshold), :] = 0
     return wf
 
 
@@ -456,6 +461,73 @@ def filterbank_block(wf: np.ndarray, valid_rows: int, tscrunch: int,
     if reverse:
         p = p[::-1]
     return np.ascontiguousarray(p.T)
+
+
+# polarization states of the two-polarization filterbank: name -> index as the
+# kernel takes it (docs/ARCHITECTURE.md, "Polarization products")
+POL_STATES = {"I": 0, "AABBCRCI": 1, "IQUV": 2}
+POL_STATE_NIFS = {"I": 1, "AABBCRCI": 4, "IQUV": 4}
+
+
+def pol_state_name(pol_state) -> str:
+    """The state's name from a name or an index; ValueError otherwise."""
+    if isinstance(pol_state, str):
+        if pol_state in POL_STATES:
+            return pol_state
+    else:
+        for name, index in POL_STATES.items():
+            if index == pol_state:
+                return name
+    raise ValueError(f"unknown polarization state {pol_state!r} "
+                     f"(one of {', '.join(POL_STATES)})")
+
+
+def pol_products_block(wf_a: np.ndarray, wf_b: np.ndarray, valid_rows: int,
+                       tscrunch: int, fscrunch: int, reverse: bool,
+                       pol_state, flags_a=None, flags_b=None) -> np.ndarray:
+    """Polarization products [R][P][C] (float64, channel fastest) of two
+    [S][L] waterfalls A = x+iy, B = u+iv of the same sky, with R, C, the cell
+    and the channel order of filterbank_block.  Per sample AA = x^2+y^2,
+    BB = u^2+v^2, CR = xu+yv, CI = yu-xv, each summed over the cell.  A row
+    whose flag is set in either ``flags_a`` or ``flags_b`` ([S], optional)
+    contributes 0 to every product.  ``pol_state`` (name or index of
+    POL_STATES): I -> AA+BB; AABBCRCI -> AA, BB, CR, CI; IQUV -> AA+BB, AA-BB,
+    2 CR, 2 CI."""
+    name = pol_state_name(pol_state)
+    wf_a, wf_b = np.asarray(wf_a), np.asarray(wf_b)
+    if wf_a.ndim != 2 or wf_a.shape != wf_b.shape:
+        raise ValueError("pol_products_block: the waterfalls differ in shape")
+    S, L = wf_a.shape
+    if (tscrunch < 1 or fscrunch < 1 or S % fscrunch != 0
+            or not tscrunch <= valid_rows <= L):
+        raise ValueError("pol_products_block: bad geometry")
+    keep = np.ones(S, dtype=bool)
+    for flags in (flags_a, flags_b):
+        if flags is not None:
+            flags = np.asarray(flags)
+            if flags.shape != (S,):
+                raise ValueError("pol_products_block: flags must be [S]")
+            keep &= flags == 0
+    R, C = valid_rows // tscrunch, S // fscrunch
+    x, y = wf_a.real.astype(np.float64), wf_a.imag.astype(np.float64)
+    u, v = wf_b.real.astype(np.float64), wf_b.imag.astype(np.float64)
+
+    def cells(p):
+        p = np.where(keep[:, None], p, 0.0)
+        p = p[:, :R * tscrunch].reshape(C, fscrunch, R, tscrunch)
+        p = p.sum(axis=(1, 3))
+        return p[::-1].T if reverse else p.T
+
+    aa, bb = cells(x * x + y * y), cells(u * u + v * v)
+    if name == "I":
+        planes = [aa + bb]
+    else:
+        cr, ci = cells(x * u + y * v), cells(y * u - x * v)
+        if name == "AABBCRCI":
+            planes = [aa, bb, cr, ci]
+        else:
+            planes = [aa + bb, aa - bb, cr + cr, ci + ci]
+    return np.ascontiguousarray(np.stack(planes, axis=1))
 
 
 def filterbank_quantize(P: np.ndarray, mean: np.ndarray,
