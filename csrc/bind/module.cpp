@@ -128,16 +128,20 @@ torch::Tensor t_build_window(int64_t n, int64_t kind, torch::Device dev) {
   return out;
 }
 
-torch::Tensor t_mean_power(torch::Tensor spec) {
+// blocks (optional): the pass-1 grid, a test surface for the fp64 drain
+torch::Tensor t_mean_power(torch::Tensor spec, int64_t blocks = 0) {
   CHECK_CUDA(spec);
   CHECK_CONTIG(spec);
   TORCH_CHECK(spec.scalar_type() == torch::kComplexFloat);
+  TORCH_CHECK(blocks >= 0 && blocks <= reduce_partials() / 2,
+              "mean_power: blocks must be 0 (default) or 1 .. ",
+              reduce_partials() / 2);
   auto partials = torch::empty({reduce_partials()},
                                spec.options().dtype(torch::kFloat64));
   auto out = torch::empty({1}, spec.options().dtype(torch::kFloat64));
   check(mean_power(cptr(spec), spec.numel(),
                    partials.data_ptr<double>(), out.data_ptr<double>(),
-                   cur_stream()),
+                   cur_stream(), (int)blocks),
         "mean_power");
   return out;
 }
@@ -168,6 +172,12 @@ void t_rfi_s1(torch::Tensor spec, double threshold, int64_t channel_count) {
 
 void t_zap_bins(torch::Tensor spec, int64_t lo, int64_t hi) {
   CHECK_CUDA(spec);
+  CHECK_CONTIG(spec);
+  TORCH_CHECK(spec.scalar_type() == torch::kComplexFloat,
+              "zap_bins: spec must be complex64");
+  TORCH_CHECK(0 <= lo && lo <= hi && hi < spec.numel(),
+              "zap_bins: need 0 <= lo <= hi < ", spec.numel(), ", got ", lo,
+              " and ", hi);
   check(zap_bins(cptr(spec), lo, hi, cur_stream()), "zap_bins");
 }
 
@@ -224,7 +234,14 @@ void t_rfi_dedisperse_fused(torch::Tensor spec, bool enable_rfi,
     zr[i].hi = (unsigned long long)ranges[i][1];
   }
   const float2* tb = nullptr;
-  if (table.has_value()) tb = cptr(*table);
+  if (table.has_value()) {
+    CHECK_CUDA(*table);
+    CHECK_CONTIG(*table);
+    TORCH_CHECK(table->scalar_type() == torch::kComplexFloat &&
+                    (size_t)table->numel() >= n,
+                "table must be complex64 with at least ", n, " factors");
+    tb = cptr(*table);
+  }
   check(rfi_dedisperse_fused(static_cast<const float2*>(cptr(spec)), dst, n,
                              mp, (float)threshold, coeff, zr,
                              (int)ranges.size(), f_min, f_c, df, dm, tb,
@@ -417,7 +434,10 @@ torch::Tensor t_boxcar(torch::Tensor cumsum, int64_t L) {
 torch::Tensor t_resample_power(torch::Tensor wf, int64_t H, int64_t W) {
   CHECK_CUDA(wf);
   CHECK_CONTIG(wf);
-  TORCH_CHECK(wf.dim() == 2);
+  TORCH_CHECK(wf.dim() == 2 && wf.scalar_type() == torch::kComplexFloat);
+  TORCH_CHECK(wf.size(0) >= 1 && wf.size(1) >= 1 && H >= 1 && W >= 1 &&
+                  H <= INT32_MAX && W <= INT32_MAX && H * W <= INT32_MAX,
+              "resample_power: rows, len, H and W must all be >= 1");
   auto out = torch::empty({H, W}, wf.options().dtype(torch::kFloat32));
   check(resample_power_2d(cptr(wf), wf.size(0), wf.size(1),
                           out.data_ptr<float>(), (int)H, (int)W, cur_stream()),
@@ -436,6 +456,9 @@ void t_normalize_by_mean(torch::Tensor img) {
 torch::Tensor t_generate_pixmap(torch::Tensor img, int64_t c0, int64_t c1,
                                 int64_t cover) {
   CHECK_CUDA(img);
+  CHECK_CONTIG(img);
+  TORCH_CHECK(img.scalar_type() == torch::kFloat32,
+              "generate_pixmap: img must be float32");
   auto out = torch::empty_like(img, img.options().dtype(torch::kInt32));
   check(generate_pixmap(img.data_ptr<float>(),
                         reinterpret_cast<uint32_t*>(out.data_ptr<int32_t>()),
@@ -449,7 +472,10 @@ std::vector<torch::Tensor> t_running_mean(torch::Tensor data,
                                           int64_t windowsize) {
   CHECK_CUDA(data);
   CHECK_CONTIG(data);
-  TORCH_CHECK(data.dim() == 2);
+  TORCH_CHECK(data.dim() == 2 && data.scalar_type() == torch::kFloat32);
+  TORCH_CHECK(windowsize >= 1 && windowsize <= data.size(0),
+              "running_mean: need 1 <= windowsize <= nsamp = ", data.size(0),
+              ", got ", windowsize);
   const size_t nsamp = data.size(0), nchan = data.size(1);
   auto ave = torch::empty({(int64_t)nchan}, data.options());
   auto out = torch::empty({(int64_t)nsamp, (int64_t)nchan},
@@ -464,17 +490,55 @@ std::vector<torch::Tensor> t_running_mean(torch::Tensor data,
   return {out, ave};
 }
 
+// out (optional): receives corr; it may be f1 or f2 itself
 std::vector<torch::Tensor> t_correlate(torch::Tensor f1, torch::Tensor f2,
-                                       double scale) {
+                                       double scale,
+                                       c10::optional<torch::Tensor> out) {
   CHECK_CUDA(f1);
   CHECK_CUDA(f2);
-  auto corr = torch::empty_like(f1);
+  CHECK_CONTIG(f1);
+  CHECK_CONTIG(f2);
+  TORCH_CHECK(f1.scalar_type() == torch::kComplexFloat &&
+                  f2.scalar_type() == torch::kComplexFloat,
+              "correlate: f1 and f2 must be complex64");
+  TORCH_CHECK(f2.numel() == f1.numel(), "correlate: f2 has ", f2.numel(),
+              " elements, f1 has ", f1.numel());
+  torch::Tensor corr;
+  if (out.has_value()) {
+    CHECK_CUDA(*out);
+    CHECK_CONTIG(*out);
+    TORCH_CHECK(out->scalar_type() == torch::kComplexFloat &&
+                    out->numel() == f1.numel(),
+                "correlate: out must match f1 in dtype and size");
+    // exactly aliased or disjoint: a partial overlap would race
+    for (const torch::Tensor* in : {&f1, &f2}) {
+      const char* a = static_cast<const char*>(in->data_ptr());
+      const char* b = static_cast<const char*>(out->data_ptr());
+      const size_t bytes = (size_t)f1.numel() * sizeof(float2);
+      TORCH_CHECK(a == b || a + bytes <= b || b + bytes <= a,
+                  "correlate: out may alias an input only exactly");
+    }
+    corr = *out;
+  } else {
+    corr = torch::empty_like(f1);
+  }
   auto mag = torch::empty({f1.numel()}, f1.options().dtype(torch::kFloat32));
   check(correlate_pointwise(cptr(f1), cptr(f2), cptr(corr),
                             mag.data_ptr<float>(), f1.numel(), (float)scale,
                             cur_stream()),
         "correlate");
   return {corr, mag};
+}
+
+torch::Tensor t_complex_abs(torch::Tensor x) {
+  CHECK_CUDA(x);
+  CHECK_CONTIG(x);
+  TORCH_CHECK(x.scalar_type() == torch::kComplexFloat,
+              "complex_abs: x must be complex64");
+  auto mag = torch::empty({x.numel()}, x.options().dtype(torch::kFloat32));
+  check(complex_abs(cptr(x), mag.data_ptr<float>(), x.numel(), cur_stream()),
+        "complex_abs");
+  return mag;
 }
 
 // ---------------- filterbank output ----------------
@@ -1320,7 +1384,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n_streams"), py::arg("window") = c10::nullopt);
   m.def("build_window", &t_build_window, py::arg("n"), py::arg("kind"),
         py::arg("device") = torch::Device(torch::kCUDA));
-  m.def("mean_power", &t_mean_power);
+  m.def("mean_power", &t_mean_power, py::arg("spec"), py::arg("blocks") = 0);
   m.def("sum_sumsq", &t_sum_sumsq);
   m.def("rfi_s1", &t_rfi_s1);
   m.def("zap_bins", &t_zap_bins);
@@ -1349,7 +1413,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("normalize_by_mean", &t_normalize_by_mean);
   m.def("generate_pixmap", &t_generate_pixmap);
   m.def("running_mean", &t_running_mean);
-  m.def("correlate", &t_correlate);
+  m.def("correlate", &t_correlate, py::arg("f1"), py::arg("f2"),
+        py::arg("scale"), py::arg("out") = py::none());
+  m.def("complex_abs", &t_complex_abs, py::arg("x"));
   m.def("filterbank_detect", &t_filterbank_detect, py::arg("wf"),
         py::arg("flags"), py::arg("valid_rows"), py::arg("tscrunch"),
         py::arg("fscrunch"), py::arg("reverse"));

@@ -63,8 +63,12 @@ hipError_t build_window(float* coef, size_t n, int kind, hipStream_t stream);
 // out: 1 double = mean.  Use reduce_partials() to size the scratch.
 int reduce_partials();  // number of fp64 partials the reductions use
 
+// blocks: pass-1 grid, 1 .. reduce_partials() / 2; 0 = the default of 1024
+// (every production call).  Pass 2 sums exactly the partials pass 1 wrote.
+// A smaller grid is the test surface for the per-thread fp64 drain, which a
+// thread reaches after 1024 trips of its loop (2^19 bins at blocks = 1).
 hipError_t mean_power(const float2* in, size_t n, double* partials,
-                      double* out_mean, hipStream_t stream);
+                      double* out_mean, hipStream_t stream, int blocks = 0);
 
 // sum and sum-of-squares over a float array (two outputs in one pass):
 // out[0] = sum, out[1] = sum of squares
@@ -78,6 +82,8 @@ hipError_t rfi_s1(float2* spec, size_t n, const double* mean_power,
                   float threshold, float norm_coeff, hipStream_t stream);
 
 // Manual zap of inclusive bin range (reference rfi_mitigation.hpp:97-157).
+// hi < lo returns hipErrorInvalidValue; the launcher does not know the
+// spectrum's length, so hi < length is the caller's to check.
 hipError_t zap_bins(float2* spec, size_t lo, size_t hi, hipStream_t stream);
 
 // Standalone coherent dedispersion, fp64 phase (reference
@@ -131,7 +137,6 @@ hipError_t sk_flags(const float2* wf, const float2* s2s4, size_t rows,
                     size_t len, float lo_corrected, float hi_corrected,
                     uint8_t* flags, unsigned* zero_count, hipStream_t stream);
 
-// Zero out flagged rows.
 // wave-local small FFT: n in {256,512,1024}, one FFT per wave (batched,
 // contiguous); tw_n = n-entry twiddle table with the sign baked in
 hipError_t fft_wave_pass(const float2* in, float2* out, uint32_t n,
@@ -143,6 +148,7 @@ hipError_t fft_wave_pass(const float2* in, float2* out, uint32_t n,
 hipError_t window_deapply(float2* wf, const float* coef, size_t total,
                           size_t len, hipStream_t stream);
 
+// Zero out flagged rows.
 hipError_t sk_zap_rows(float2* wf, const uint8_t* flags, size_t rows,
                        size_t len, hipStream_t stream);
 
@@ -447,7 +453,8 @@ hipError_t r2c_post_process(const float2* z, float2* x, size_t m,
 // Area-averaged power resample of [rows][len] complex waterfall to [H][W]
 // floats; one workgroup (64 lanes) per output pixel with LDS tree reduce
 // (reference resample_spectrum_3, simplify_spectrum.hpp:423-620; wg=64 was
-// measured fastest on wave64 GCN — kept for CDNA4).
+// measured fastest on wave64 GCN — kept for CDNA4).  rows, len, out_h and
+// out_w must all be >= 1, else hipErrorInvalidValue and no launch.
 hipError_t resample_power_2d(const float2* wf, size_t rows, size_t len,
                              float* out, int out_h, int out_w,
                              hipStream_t stream);
@@ -459,13 +466,20 @@ hipError_t normalize_by_mean(float* img, size_t n, const double* sum,
 
 // intensity [0,1] → ARGB32 lerp color_0..color_1, else overflow color
 // (reference simplify_spectrum.hpp:700-731, config.hpp:60-68).
+// Rounding rule, shared with srtb_amd.ref.generate_pixmap: each 8-bit channel
+// is a + (b - a) * x rounded to the nearest integer, ties away from zero
+// (roundf; the reference truncates).  In range means 0 <= x <= 1, so -0.0 is
+// in range and NaN, +-inf and anything below 0 or above 1 take the overflow
+// colour.
 hipError_t generate_pixmap(const float* intensity, uint32_t* out, size_t n,
                            uint32_t color0, uint32_t color1,
                            uint32_t color_overflow, hipStream_t stream);
 
 // ---------------- misc device algorithms ----------------
 // Running-mean 1-bit threshold, time-major [nsamp][nchan]
-// (reference algorithm/running_mean.hpp:31-77).
+// (reference algorithm/running_mean.hpp:31-77).  1 <= windowsize <= nsamp,
+// else hipErrorInvalidValue and no launch (the mirrored tail indexes
+// nsamp + i - windowsize).
 hipError_t running_mean_init(const float* data, size_t nsamp, size_t nchan,
                              size_t windowsize, float* ave, hipStream_t stream);
 hipError_t running_mean(const float* data, size_t nsamp, size_t nchan,
@@ -477,7 +491,9 @@ hipError_t complex_abs(const float2* x, float* mag, size_t n,
                        hipStream_t stream);
 
 // correlator pointwise: corr[i] = scale * f1[i]*conj(f2[i]); mag[i] = |corr[i]|
-// (reference src/correlator.cpp:116-140; mag may be null).
+// (reference src/correlator.cpp:116-140; mag may be null).  corr may alias
+// f1 or f2 exactly (srtb-correlator writes over f1): every thread reads its
+// element of both inputs before it writes.  A partial overlap is not allowed.
 hipError_t correlate_pointwise(const float2* f1, const float2* f2,
                                float2* corr, float* mag, size_t n, float scale,
                                hipStream_t stream);

@@ -115,10 +115,11 @@ __global__ void k_complex_abs(const float2* __restrict__ x,
     mag[i] = sqrtf(norm2(x[i]));
 }
 
-__global__ void k_correlate(const float2* __restrict__ f1,
-                            const float2* __restrict__ f2,
-                            float2* __restrict__ corr, float* __restrict__ mag,
-                            size_t n, float scale) {
+// corr may alias f1 or f2 exactly (srtb-correlator writes over f1), so none
+// of the three is __restrict__: a thread reads its element of both inputs
+// before it writes.
+__global__ void k_correlate(const float2* f1, const float2* f2, float2* corr,
+                            float* __restrict__ mag, size_t n, float scale) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
@@ -136,7 +137,10 @@ __global__ void k_correlate(const float2* __restrict__ f1,
 hipError_t resample_power_2d(const float2* wf, size_t rows, size_t len,
                              float* out, int out_h, int out_w,
                              hipStream_t stream) {
+  if (rows < 1 || len < 1 || out_h < 1 || out_w < 1)
+    return hipErrorInvalidValue;
   const size_t pixels = (size_t)out_h * out_w;
+  if (pixels > 0x7FFFFFFFull) return hipErrorInvalidValue;  // grid.x, int pix
   hipLaunchKernelGGL(k_resample_power, dim3((uint32_t)pixels), dim3(64), 0,
                      stream, wf, rows, len, out, out_h, out_w);
   SRTB_CHECK_LAUNCH();
@@ -163,9 +167,10 @@ hipError_t generate_pixmap(const float* intensity, uint32_t* out, size_t n,
 hipError_t running_mean_init(const float* data, size_t nsamp, size_t nchan,
                              size_t windowsize, float* ave,
                              hipStream_t stream) {
-  (void)nsamp;
-  hipLaunchKernelGGL(k_running_mean_init, grid_for(nchan), dim3(kBlock), 0,
-                     stream, data, nchan, windowsize, ave);
+  if (windowsize < 1 || windowsize > nsamp) return hipErrorInvalidValue;
+  // one thread per channel, no grid-stride loop: the grid is not capped
+  hipLaunchKernelGGL(k_running_mean_init, grid_for(nchan, kBlock, INT32_MAX),
+                     dim3(kBlock), 0, stream, data, nchan, windowsize, ave);
   SRTB_CHECK_LAUNCH();
   return hipSuccess;
 }
@@ -173,7 +178,10 @@ hipError_t running_mean_init(const float* data, size_t nsamp, size_t nchan,
 hipError_t running_mean(const float* data, size_t nsamp, size_t nchan,
                         uint8_t* out, size_t windowsize, float* ave,
                         hipStream_t stream) {
-  hipLaunchKernelGGL(k_running_mean, grid_for(nchan), dim3(kBlock), 0, stream,
+  // nsamp + i - windowsize in the mirrored tail would underflow
+  if (windowsize < 1 || windowsize > nsamp) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_running_mean, grid_for(nchan, kBlock, INT32_MAX),
+                     dim3(kBlock), 0, stream,
                      data, nsamp, nchan, out, windowsize, ave);
   SRTB_CHECK_LAUNCH();
   return hipSuccess;

@@ -707,11 +707,13 @@ __global__ void k_peaks_finish(const unsigned long long* __restrict__ partial,
 int reduce_partials() { return 2 * kReducePartials; }
 
 hipError_t mean_power(const float2* in, size_t n, double* partials,
-                      double* out_mean, hipStream_t stream) {
-  hipLaunchKernelGGL(k_mean_power_pass1, dim3(kReducePartials), dim3(kBlock),
+                      double* out_mean, hipStream_t stream, int blocks) {
+  if (blocks == 0) blocks = kReducePartials;
+  if (blocks < 1 || blocks > kReducePartials) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_mean_power_pass1, dim3((uint32_t)blocks), dim3(kBlock),
                      0, stream, in, n, partials);
   hipLaunchKernelGGL(k_reduce_partials_mean, dim3(1), dim3(kBlock), 0, stream,
-                     partials, kReducePartials, n, out_mean);
+                     partials, blocks, n, out_mean);
   SRTB_CHECK_LAUNCH();
   return hipSuccess;
 }
@@ -869,7 +871,9 @@ hipError_t sk_zap_rows(float2* wf, const uint8_t* flags, size_t rows,
 
 hipError_t sk_v1_stats(const float2* wf, size_t M, size_t bins, float2* s2s4,
                        hipStream_t stream) {
-  hipLaunchKernelGGL(k_sk_v1_stats, grid_for(bins), dim3(kBlock), 0, stream,
+  // one thread per bin, no grid-stride loop: the grid is not capped
+  hipLaunchKernelGGL(k_sk_v1_stats, grid_for(bins, kBlock, INT32_MAX),
+                     dim3(kBlock), 0, stream,
                      wf, M, bins, s2s4);
   SRTB_CHECK_LAUNCH();
   return hipSuccess;

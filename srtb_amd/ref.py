@@ -740,13 +740,24 @@ COLOR_OVERFLOW = 0xFFE0E1CC
 
 def generate_pixmap(intensity: np.ndarray) -> np.ndarray:
     """intensity in [0,1] → ARGB32 via per-channel lerp between COLOR_0 and
-    COLOR_1; out-of-range → COLOR_OVERFLOW (reference simplify_spectrum.hpp:700-731)."""
+    COLOR_1; out-of-range → COLOR_OVERFLOW (reference simplify_spectrum.hpp:700-731).
+
+    Rounding rule, shared with the HIP kernel (csrc/include/srtb_kernels.h):
+    each channel is c0 + (c1 - c0) * x rounded to the nearest integer, ties
+    away from zero (C's roundf, not NumPy's ties-to-even round; the reference
+    truncates).  In range means 0 <= x <= 1: -0.0 is in range, NaN and
+    infinities are not."""
     x = np.asarray(intensity, dtype=np.float64)
     out = np.empty(x.shape, dtype=np.uint32)
     ok = (x >= 0) & (x <= 1)
+    x = np.where(ok, x, 0.0)
 
     def chan(c0, c1):
-        return np.clip(np.round(c0 + (c1 - c0) * x), 0, 255).astype(np.uint32)
+        # the value is in [0, 255], where away from zero is floor(v + 1/2);
+        # float64 holds v exactly for any float32 x large enough to bring it
+        # near a half-integer
+        v = c0 + (c1 - c0) * x
+        return np.clip(np.floor(v + 0.5), 0, 255).astype(np.uint32)
 
     a = chan((COLOR_0 >> 24) & 0xFF, (COLOR_1 >> 24) & 0xFF)
     r = chan((COLOR_0 >> 16) & 0xFF, (COLOR_1 >> 16) & 0xFF)

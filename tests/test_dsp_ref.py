@@ -259,6 +259,26 @@ def test_generate_pixmap_colors():
     assert img[3] == ref.COLOR_OVERFLOW
 
 
+def test_generate_pixmap_rounds_ties_away_from_zero():
+    """The rule of csrc/include/srtb_kernels.h.  With the GUI colours the
+    lerp is an exact half-integer at three intensities of the grid j / 4096:
+    blue 0x33 + 190 x = 98.5 at 0.25, red 0x1F + 20 x = 38.5 at 0.375 and
+    48.5 at 0.875; ties-to-even gave 0x62, 0x26 and 0x30."""
+    x = np.array([0.25, 0.375, 0.875], dtype=np.float32)
+    img = ref.generate_pixmap(x)
+    assert img[0] & 0xFF == 0x63
+    assert (img[1] >> 16) & 0xFF == 0x27
+    assert (img[2] >> 16) & 0xFF == 0x31
+    # the other channels of those three pixels are no ties
+    assert [hex(int(v)) for v in img] == ["0xff244f63", "0xff27677a",
+                                          "0xff31c9d9"]
+    # -0.0 is in range; NaN and infinities are not
+    edge = ref.generate_pixmap(np.array([-0.0, np.nan, np.inf, -np.inf],
+                                        dtype=np.float32))
+    assert edge[0] == ref.COLOR_0
+    assert (edge[1:] == ref.COLOR_OVERFLOW).all()
+
+
 def test_normalize_by_mean():
     img = np.full((4, 4), 3.0)
     out = ref.normalize_by_mean(img)
