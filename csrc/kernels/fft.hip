@@ -1554,6 +1554,336 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// ---------------------------------------------------------------------------
+// Length-64 final passes with compile-time n = 64 and F: the same loads,
+// butterflies, stores and accumulation order as k_fft_dif_final and
+// k_fft_dif_final_r2c (which stay the path of every other shape and the
+// bit-for-bit yardstick of these), with the address work taken out of the
+// per-element loops:
+//  - load: a wave loads one row per instruction, so the row and its
+//    dif_addr() are scalar; a lane adds its lane id and a fixed swizzle;
+//  - stages: thread t owns quartet t & 15 of rows (t >> 4) + 16 i, so its
+//    four LDS offsets and three twiddles are fixed per stage and the rows
+//    differ by a constant; j == 0 selects the unmultiplied value (a product
+//    with (1, 0) would change the sign of a zero);
+//  - store: f is fixed per thread and k = (t >> log2 F) + (256/F) i; rev4 and
+//    the swizzle are bit permutations / xor-linear, so trip i is the thread's
+//    fixed offset xor a constant, and the output index advances by a constant.
+// Which wave loads which row, and the workgroup barriers, are the generic
+// kernels' (wave-owned rows without those barriers measured no faster:
+// docs/ROADMAP.md, negative results).
+// ---------------------------------------------------------------------------
+constexpr int kDif64Ldst = 66;
+
+// Rounding of the generic kernels, spelled out.  With -ffp-contract=fast the
+// compiler contracts the generic kernels' products its own way: of the three
+// twiddle products of a butterfly, x1 w1 becomes
+//   (fma(a.x, b.x, -(a.y b.y)), fma(a.y, b.x, a.x b.y))
+// while x2 w2 and x3 w3 keep an uncontracted real part,
+//   (a.x b.x - a.y b.y, fma(a.x, b.y, a.y b.x)),
+// |v|^2 is fma(v.x, v.x, v.y v.y) in both precisions, and the SK sum of
+// squares adds the rounded p p (all six generic instances agree, read from
+// their gfx950 assembly).  Straight-line code gets other choices, so these
+// kernels state the forms; mul_rounded() keeps a product out of the
+// contraction pass's sight.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+  float p = a * b;
+  asm("" : "+v"(p));
+  return p;
+}
+__device__ __forceinline__ float2 dif_cmul_w1(float2 a, float2 b) {
+  return make_float2(__builtin_fmaf(a.x, b.x, -(a.y * b.y)),
+                     __builtin_fmaf(a.y, b.x, a.x * b.y));
+}
+__device__ __forceinline__ float2 dif_cmul_w23(float2 a, float2 b) {
+  return make_float2(mul_rounded(a.x, b.x) - mul_rounded(a.y, b.y),
+                     __builtin_fmaf(a.x, b.y, a.y * b.x));
+}
+__device__ __forceinline__ double dif_norm_f64(float2 v) {
+  return __builtin_fma((double)v.x, (double)v.x, (double)v.y * (double)v.y);
+}
+
+__host__ __device__ constexpr int dif64_swz(int i) {
+  return i ^ ((i >> 2) & 31);
+}
+__host__ __device__ constexpr int dif64_rev4(int k) {
+  return ((k & 3) << 4) | (k & 12) | ((k >> 4) & 3);
+}
+
+template <int SIGN, bool TW>
+__device__ __forceinline__ void dif64_bfly(float2* __restrict__ row, int e0,
+                                           int e1, int e2, int e3, bool jz,
+                                           float2 w1, float2 w2, float2 w3) {
+  const float2 a = row[e0];
+  const float2 bv = row[e1];
+  const float2 c = row[e2];
+  const float2 dv = row[e3];
+  const float2 t0 = make_float2(a.x + c.x, a.y + c.y);
+  const float2 t1 = make_float2(a.x - c.x, a.y - c.y);
+  const float2 t2 = make_float2(bv.x + dv.x, bv.y + dv.y);
+  const float2 dmy = make_float2(bv.x - dv.x, bv.y - dv.y);
+  const float2 t3 = (SIGN > 0) ? make_float2(-dmy.y, dmy.x)
+                               : make_float2(dmy.y, -dmy.x);
+  const float2 x0 = make_float2(t0.x + t2.x, t0.y + t2.y);
+  const float2 x1 = make_float2(t1.x + t3.x, t1.y + t3.y);
+  const float2 x2 = make_float2(t0.x - t2.x, t0.y - t2.y);
+  const float2 x3 = make_float2(t1.x - t3.x, t1.y - t3.y);
+  row[e0] = x0;
+  if constexpr (TW) {
+    const float2 y1 = dif_cmul_w1(x1, w1);
+    const float2 y2 = dif_cmul_w23(x2, w2);
+    const float2 y3 = dif_cmul_w23(x3, w3);
+    row[e1] = make_float2(jz ? x1.x : y1.x, jz ? x1.y : y1.y);
+    row[e2] = make_float2(jz ? x2.x : y2.x, jz ? x2.y : y2.y);
+    row[e3] = make_float2(jz ? x3.x : y3.x, jz ? x3.y : y3.y);
+  } else {
+    row[e1] = x1;
+    row[e2] = x2;
+    row[e3] = x3;
+  }
+}
+
+// dif_addr()'s input block offset of a wave-uniform instance, for scalar
+// registers: row_len < 2^32 (the launchers check it), so J, the digits and
+// the block index P fit 32 bits; digits past n_prefix have no bits and a
+// zero coefficient (the launchers clear them), so no branch per digit.
+__device__ __forceinline__ unsigned long long dif64_in_blk(
+    unsigned long long id, const DifFinalDescDev& d) {
+  const uint32_t J = (uint32_t)id & ((1u << d.j_bits) - 1u);
+  const unsigned long long row = id >> d.j_bits;
+  uint32_t x = J, P = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint32_t dig = x & ((1u << d.pf_bits[w]) - 1u);
+    P += dig * (uint32_t)d.pf_coef[w];
+    x >>= d.pf_bits[w];
+  }
+  return row * d.row_len + ((unsigned long long)P << 6);
+}
+
+// rows of X <- instances instance_of(row); ROWS a multiple of 16
+template <int ROWS, typename InstFn>
+__device__ __forceinline__ void dif64_load(const float2* __restrict__ in,
+                                           float2* __restrict__ X,
+                                           const DifFinalDescDev& d,
+                                           InstFn instance_of) {
+  constexpr int PER = ROWS / 4;  // rows per wave
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63;
+  const int sl = dif64_swz(lane);
+  float2 tmp[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    tmp[k] = in[dif64_in_blk(instance_of(wv + 4 * k), d) + lane];
+  }
+#pragma unroll
+  for (int k = 0; k < PER; ++k)
+    X[(wv + 4 * k) * kDif64Ldst + sl] = tmp[k];
+  __syncthreads();
+}
+
+// the three radix-4 DIF stages of every row; no barrier after the last one
+template <int SIGN, int ROWS>
+__device__ __forceinline__ void dif64_stages(float2* __restrict__ X,
+                                             const float2* __restrict__ tw_n) {
+  const int bb = threadIdx.x & 15;
+  float2* __restrict__ base = X + (threadIdx.x >> 4) * kDif64Ldst;
+  const float2 one = make_float2(1.f, 0.f);
+  {  // L = 64, M = 16: j = bb, g = 0
+    const int j = bb;
+    const int e0 = dif64_swz(j), e1 = dif64_swz(j + 16);
+    const int e2 = dif64_swz(j + 32), e3 = dif64_swz(j + 48);
+    const float2 w1 = tw_n[j], w2 = tw_n[2 * j], w3 = tw_n[3 * j];
+#pragma unroll
+    for (int it = 0; it < ROWS / 16; ++it)
+      dif64_bfly<SIGN, true>(base + it * 16 * kDif64Ldst, e0, e1, e2, e3,
+                             j == 0, w1, w2, w3);
+  }
+  __syncthreads();
+  {  // L = 16, M = 4: j = bb & 3, g = 16 (bb >> 2); W_16^x = W_64^(4x)
+    const int j = bb & 3;
+    const int g = (bb >> 2) << 4;
+    const int e0 = dif64_swz(g + j), e1 = dif64_swz(g + j + 4);
+    const int e2 = dif64_swz(g + j + 8), e3 = dif64_swz(g + j + 12);
+    const float2 w1 = tw_n[4 * j], w2 = tw_n[8 * j], w3 = tw_n[12 * j];
+#pragma unroll
+    for (int it = 0; it < ROWS / 16; ++it)
+      dif64_bfly<SIGN, true>(base + it * 16 * kDif64Ldst, e0, e1, e2, e3,
+                             j == 0, w1, w2, w3);
+  }
+  __syncthreads();
+  {  // L = 4, M = 1: j = 0 always, g = 4 bb
+    const int g = bb << 2;
+    const int e0 = dif64_swz(g), e1 = dif64_swz(g + 1);
+    const int e2 = dif64_swz(g + 2), e3 = dif64_swz(g + 3);
+#pragma unroll
+    for (int it = 0; it < ROWS / 16; ++it)
+      dif64_bfly<SIGN, false>(base + it * 16 * kDif64Ldst, e0, e1, e2, e3,
+                              true, one, one, one);
+  }
+}
+
+template <int SIGN, bool SK, int F>
+__global__ void __launch_bounds__(256)
+    k_fft_dif64_final(const float2* __restrict__ in, float2* __restrict__ out,
+                      DifFinalDescDev d, const float2* __restrict__ tw_n,
+                      float2* __restrict__ sk_partials, int wgs_per_row) {
+  static_assert(F == 16 || F == 32, "rows per workgroup: a multiple of 16");
+  constexpr int FL = (F == 32) ? 5 : 4;
+  constexpr int KS = 256 / F;  // k advances by this per store trip
+  __shared__ float2 X[F * kDif64Ldst];
+  const unsigned long long fft0 = (unsigned long long)blockIdx.x << FL;
+
+  dif64_load<F>(in, X, d,
+                [&](int r) { return fft0 + (unsigned long long)r; });
+  dif64_stages<SIGN, F>(X, tw_n);
+  __syncthreads();
+
+  // ---- store: element (f, k = klo + KS i) of the generic kernel's loop ----
+  const int f = threadIdx.x & (F - 1);
+  const int klo = threadIdx.x >> FL;
+  unsigned long long in_blk, obase;
+  dif_addr(fft0 + f, d, in_blk, obase);
+  const float2* __restrict__ xr = X + f * kDif64Ldst;
+  const int s0 = dif64_swz(dif64_rev4(klo));
+  float2* __restrict__ op =
+      out + obase + (unsigned long long)klo * d.out_elem_coef;
+  const unsigned long long step = (unsigned long long)KS * d.out_elem_coef;
+  float sk2 = 0.0f, sk4 = 0.0f;
+#pragma unroll
+  for (int it = 0; it < 64 / KS; ++it) {
+    const float2 v = xr[s0 ^ dif64_swz(dif64_rev4(KS * it))];
+    op[(unsigned long long)it * step] = v;
+    if constexpr (SK) {
+      const float p = __builtin_fmaf(v.x, v.x, v.y * v.y);
+      sk2 += p;
+      sk4 += mul_rounded(p, p);
+    }
+  }
+  if constexpr (SK) {
+    const float b2 = block_reduce_sum(sk2);
+    const float b4 = block_reduce_sum(sk4);
+    if (threadIdx.x == 0) {
+      const unsigned long long row = fft0 >> d.j_bits;
+      const unsigned long long wg_in_row =
+          (fft0 & ((1ull << d.j_bits) - 1)) >> FL;
+      sk_partials[row * wgs_per_row + wg_in_row] = make_float2(b2, b4);
+    }
+  }
+}
+
+// r2c: the packed length M = row_len is below 2^32 here (the launcher checks
+// it), so output indices are 32-bit and their conversion to double is exact.
+template <bool MEANP, int F>
+__global__ void __launch_bounds__(256)
+    k_fft_dif64_final_r2c(const float2* __restrict__ in,
+                          float2* __restrict__ out, DifFinalDescDev d,
+                          const float2* __restrict__ tw_n,
+                          double* __restrict__ partials, uint32_t tuning) {
+  static_assert(F == 16 || F == 32, "rows per side: a multiple of 16");
+  constexpr int FL = (F == 32) ? 5 : 4;
+  constexpr int KS = 256 / F;
+  __shared__ float2 X[2 * F * kDif64Ldst];
+  const unsigned long long P = 1ull << d.j_bits;
+  const unsigned long long m = d.row_len;
+  const double inv_m = 1.0 / (double)m;
+  const bool row0 = blockIdx.x == gridDim.x - 1;
+  double acc = 0.0;
+  unsigned int w = blockIdx.x;
+
+  if (!row0) {
+    w = xcd_swizzle(blockIdx.x, gridDim.x - 1, tuning);
+    const unsigned long long j0 = ((unsigned long long)w << FL) + 1;
+    dif64_load<2 * F>(in, X, d, [&](int r) {
+      return r < F ? j0 + (unsigned long long)r
+                   : P - (j0 + (unsigned long long)(r - F));
+    });
+    dif64_stages<-1, 2 * F>(X, tw_n);
+    __syncthreads();
+
+    // ---- store: pair (own (f, k), mirror (F + f, 63 - k)), k = klo + KS i;
+    // trips with KS i < 32 have the own element as the driver ----
+    const int f = threadIdx.x & (F - 1);
+    const int klo = threadIdx.x >> FL;
+    const unsigned long long J = j0 + f;
+    const bool self_paired = J == (P >> 1);  // driven from k < 32 only
+    const float2* __restrict__ xo = X + f * kDif64Ldst;
+    const float2* __restrict__ xm_ = X + (F + f) * kDif64Ldst;
+    const int s0 = dif64_swz(dif64_rev4(klo));
+    const uint32_t ko_low = (uint32_t)(J + (unsigned long long)klo * P);
+    const uint32_t ko_high =
+        (uint32_t)((P - J) + (unsigned long long)(63 - klo) * P);
+    const uint32_t kstep = (uint32_t)((unsigned long long)KS * P);
+#pragma unroll
+    for (int it = 0; it < 64 / KS; ++it) {
+      const bool low = KS * it < 32;
+      if (!low && self_paired) continue;
+      const int s = s0 ^ dif64_swz(dif64_rev4(KS * it));
+      const float2 own = xo[s];
+      const float2 mir = xm_[s ^ dif64_swz(63)];
+      const uint32_t ko = low ? ko_low + (uint32_t)it * kstep
+                              : ko_high - (uint32_t)it * kstep;
+      const float phiw = (float)(-M_PI * (double)ko * inv_m);
+      float2 xk, xm;
+      r2c_pair_combine(low ? own : mir, low ? mir : own, phiw, xk, xm);
+      out[ko] = xk;
+      out[m - ko] = xm;
+      if constexpr (MEANP) {
+        acc += dif_norm_f64(xk);
+        acc += dif_norm_f64(xm);
+      }
+    }
+  } else {
+    // instance 0 alone (one workgroup of the grid): one row, 16 quartets
+    if (threadIdx.x < 64)
+      X[dif64_swz((int)threadIdx.x)] = in[threadIdx.x];
+    __syncthreads();
+    const int bb = threadIdx.x & 15;
+    const bool act = threadIdx.x < 16;
+    if (act)
+      dif64_bfly<-1, true>(X, dif64_swz(bb), dif64_swz(bb + 16),
+                           dif64_swz(bb + 32), dif64_swz(bb + 48), bb == 0,
+                           tw_n[bb], tw_n[2 * bb], tw_n[3 * bb]);
+    __syncthreads();
+    if (act) {
+      const int j = bb & 3, g = (bb >> 2) << 4;
+      dif64_bfly<-1, true>(X, dif64_swz(g + j), dif64_swz(g + j + 4),
+                           dif64_swz(g + j + 8), dif64_swz(g + j + 12),
+                           j == 0, tw_n[4 * j], tw_n[8 * j], tw_n[12 * j]);
+    }
+    __syncthreads();
+    if (act) {
+      const float2 one = make_float2(1.f, 0.f);
+      const int g = bb << 2;
+      dif64_bfly<-1, false>(X, dif64_swz(g), dif64_swz(g + 1),
+                            dif64_swz(g + 2), dif64_swz(g + 3), true, one,
+                            one, one);
+    }
+    __syncthreads();
+    // element k pairs with element 64 - k; k = 0 stands alone and k = 32
+    // (output M/2) is its own partner
+    const int k = threadIdx.x;
+    if (k <= 32) {
+      const float2 zk = X[dif64_swz(dif64_rev4(k))];
+      const float2 zm = X[dif64_swz(dif64_rev4(k == 0 ? 0 : 64 - k))];
+      const unsigned long long ko = (unsigned long long)k * P;
+      const float phiw = (float)(-M_PI * (double)ko * inv_m);
+      float2 xk, xm;
+      r2c_pair_combine(zk, zm, phiw, xk, xm);
+      out[ko] = xk;
+      if constexpr (MEANP) acc += dif_norm_f64(xk);
+      if (k != 0 && k != 32) {
+        out[m - ko] = xm;
+        if constexpr (MEANP) acc += dif_norm_f64(xm);
+      }
+    }
+  }
+  if constexpr (MEANP) {
+    const double b = block_reduce_sum(acc);
+    if (threadIdx.x == 0) partials[w] = b;
+  }
+}
+
 // Mean from the fused final pass's partials.  There is one per workgroup,
 // P/2F + 1 of them (131073 at the 2^30-sample block): k_r2c_post_finish_mean's
 // 256 threads with one load in flight each took 0.21 ms over them.  1024
@@ -2111,6 +2441,61 @@ hipError_t r2c_mean_from_power(const float2* power_partials,
   return hipSuccess;
 }
 
+// SRTB_FFT_DIF_SPEC=0: length-64 final passes run the generic kernels too
+static bool dif_spec_enabled() {
+  const char* e = std::getenv("SRTB_FFT_DIF_SPEC");
+  return !(e && std::atoi(e) == 0);
+}
+
+namespace {
+// the specialised kernels take length 64, F of 16 or 32 and rows below 2^32
+bool dif64_applies(const DifFinalDesc& hd, int F) {
+  return hd.n == 64 && (F == 16 || F == 32) && hd.out_c2 < (1ull << 32) &&
+         dif_spec_enabled();
+}
+
+// dif64_in_blk() walks all four digits: unused ones contribute nothing
+DifFinalDescDev dif64_desc(DifFinalDescDev d) {
+  for (int i = d.n_prefix; i < 4; ++i) {
+    d.pf_bits[i] = 0;
+    d.pf_coef[i] = 0;
+  }
+  return d;
+}
+
+template <int F>
+void launch_dif64_final(const float2* in, float2* out,
+                        const DifFinalDescDev& d, uint32_t grid, int sign,
+                        const float2* tw_n, float2* sk_partials,
+                        int wgs_per_row, hipStream_t stream) {
+#define DIF64_LAUNCH(SIGN, SK)                                             \
+  hipLaunchKernelGGL((k_fft_dif64_final<SIGN, SK, F>), dim3(grid),         \
+                     dim3(256), 0, stream, in, out, d, tw_n, sk_partials,  \
+                     wgs_per_row)
+  if (sign < 0) {
+    if (sk_partials) DIF64_LAUNCH(-1, true); else DIF64_LAUNCH(-1, false);
+  } else {
+    if (sk_partials) DIF64_LAUNCH(1, true); else DIF64_LAUNCH(1, false);
+  }
+#undef DIF64_LAUNCH
+}
+
+template <int F>
+void launch_dif64_final_r2c(const float2* in, float2* out,
+                            const DifFinalDescDev& d, int grid,
+                            const float2* tw_n, double* mean_partials,
+                            uint32_t tuning, hipStream_t stream) {
+  if (mean_partials)
+    hipLaunchKernelGGL((k_fft_dif64_final_r2c<true, F>), dim3(grid),
+                       dim3(256), 0, stream, in, out, d, tw_n, mean_partials,
+                       tuning);
+  else
+    hipLaunchKernelGGL((k_fft_dif64_final_r2c<false, F>), dim3(grid),
+                       dim3(256), 0, stream, in, out, d, tw_n, nullptr,
+                       tuning);
+}
+}  // namespace
+
 hipError_t fft_dif_final(const float2* in, float2* out,
                          const DifFinalDesc& hd, size_t n_ffts, int F,
                          int sign, const float2* tw_n, float2* sk_partials,
@@ -2141,6 +2526,17 @@ hipError_t fft_dif_final(const float2* in, float2* out,
     const unsigned long long per_row = 1ull << d.j_bits;  // instances/row
     if (per_row % F != 0) return hipErrorInvalidValue;
     wgs_per_row = (int)(per_row / F);
+  }
+  if (dif64_applies(hd, F)) {
+    d = dif64_desc(d);
+    if (F == 32)
+      launch_dif64_final<32>(in, out, d, grid, sign, tw_n, sk_partials,
+                             wgs_per_row, stream);
+    else
+      launch_dif64_final<16>(in, out, d, grid, sign, tw_n, sk_partials,
+                             wgs_per_row, stream);
+    SRTB_CHECK_LAUNCH();
+    return hipSuccess;
   }
   if (sign < 0) {
     if (sk_partials)
@@ -2203,6 +2599,21 @@ hipError_t fft_dif_final_r2c(const float2* in, float2* out,
   // SRTB_FFT_R2C_XCD=0: no XCD remap of the pair workgroups
   const char* xe = std::getenv("SRTB_FFT_R2C_XCD");
   const uint32_t tuning = (xe && std::atoi(xe) == 0) ? 0u : 1u;
+  if (dif64_applies(hd, F)) {
+    d = dif64_desc(d);
+    if (F == 32)
+      launch_dif64_final_r2c<32>(in, out, d, grid, tw_n, mean_partials,
+                                 tuning, stream);
+    else
+      launch_dif64_final_r2c<16>(in, out, d, grid, tw_n, mean_partials,
+                                 tuning, stream);
+    if (mean_partials)
+      hipLaunchKernelGGL(k_r2c_final_finish_mean, dim3(1), dim3(1024), 0,
+                         stream, mean_partials, grid, (size_t)hd.out_c2,
+                         out_mean);
+    SRTB_CHECK_LAUNCH();
+    return hipSuccess;
+  }
   if (mean_partials) {
     hipLaunchKernelGGL((k_fft_dif_final_r2c<true>), dim3(grid), dim3(256),
                        lds_bytes, stream, in, out, d, tw_n, mean_partials,
