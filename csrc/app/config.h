@@ -213,6 +213,10 @@ struct Config {
   // two-polarization formats: "" = one file per data stream; I, AABBCRCI or
   // IQUV = one file of polarization products from both streams
   std::string filterbank_polarization;
+  // incoherent DM-offset search on the filterbank plane: offsets in pc cm^-3
+  // around dm (empty = off) and the candidates text file
+  std::vector<double> incoherent_dm_offsets;
+  std::string incoherent_output_path;
   // pulsar folding ("" = off), twin of the Python keys: period (s), its
   // derivative (s/s), phase bins, phase (turns) at stream sample 0, blocks
   // per sub-integration (0 = one for the whole run)
@@ -291,6 +295,12 @@ inline void Config::assign(const std::string& key, const std::string& raw0) {
   else if (key == "gui_pixmap_width") gui_pixmap_width = I();
   else if (key == "gui_pixmap_height") gui_pixmap_height = I();
   else if (key == "log_level") log_level = (int)Expr::eval_int(raw);
+  else if (key == "incoherent_dm_offsets") {
+    incoherent_dm_offsets.clear();
+    for (auto& p : split_list(raw))
+      incoherent_dm_offsets.push_back(Expr::eval(p));
+  }
+  else if (key == "incoherent_output_path") incoherent_output_path = raw;
   else if (key == "filterbank_output_path") filterbank_output_path = raw;
   else if (key == "filterbank_tscrunch") filterbank_tscrunch = I();
   else if (key == "filterbank_fscrunch") filterbank_fscrunch = I();
@@ -393,6 +403,13 @@ inline std::string Config::dump() const {
   }
   if (!filterbank_polarization.empty())
     o << "filterbank_polarization = " << filterbank_polarization << "\n";
+  if (!incoherent_dm_offsets.empty()) {
+    o << "incoherent_dm_offsets = ";
+    for (size_t i = 0; i < incoherent_dm_offsets.size(); ++i)
+      o << (i ? "," : "") << incoherent_dm_offsets[i];
+    o << "\n"
+      << "incoherent_output_path = " << incoherent_output_path << "\n";
+  }
   if (!fold_output_path.empty()) {
     const auto prec = o.precision(17);
     o << "fold_output_path = " << fold_output_path << "\n"

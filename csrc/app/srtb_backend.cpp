@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../engine/engine.h"
+#include "../engine/incoherent_search.h"
 #include "../engine/pol_combiner.h"
 #include "comm.h"
 #include "config.h"
@@ -203,7 +204,27 @@ int main(int argc, char** argv) {
                   "each other (a filterbank file holds one DM)");
     return 2;
   }
-  if (fil_mode) {
+  // incoherent DM-offset search (incoherent_dm_offsets): it consumes the
+  // per-stream power plane, with or without a filterbank file
+  const bool incoh_mode = !cfg.incoherent_dm_offsets.empty();
+  if (incoh_mode != !cfg.incoherent_output_path.empty()) {
+    SRTB_APP_LOGE("config: incoherent_dm_offsets and incoherent_output_path "
+                  "need each other");
+    return 2;
+  }
+  if (incoh_mode && trial_mode) {
+    SRTB_APP_LOGE("config: incoherent_dm_offsets and dm_trial_list exclude "
+                  "each other (the offsets are searched around the one "
+                  "coherent dm)");
+    return 2;
+  }
+  if (incoh_mode && !cfg.filterbank_polarization.empty()) {
+    SRTB_APP_LOGE("config: incoherent_dm_offsets and filterbank_polarization "
+                  "exclude each other (the search runs on per-stream planes)");
+    return 2;
+  }
+  const bool plane_mode = fil_mode || incoh_mode;
+  if (plane_mode) {
     const size_t t = cfg.filterbank_tscrunch, f = cfg.filterbank_fscrunch;
     auto pow2 = [](size_t x) { return x && !(x & (x - 1)); };
     if (!pow2(t) || t > srtb_hip::kFilterbankMaxTscrunch || !pow2(f) ||
@@ -216,7 +237,7 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  const size_t fil_t = fil_mode ? cfg.filterbank_tscrunch : 1;
+  const size_t fil_t = plane_mode ? cfg.filterbank_tscrunch : 1;
 
   // polarization products (filterbank_polarization): the two per-polarization
   // engines make no planes of their own, one PolCombiner joins them
@@ -318,7 +339,7 @@ int main(int argc, char** argv) {
   ec.max_boxcar_length = cfg.signal_detect_max_boxcar_length;
   ec.nsamps_reserved = reserved;
   ec.max_dm_trials = (int)trial_dms.size();
-  if (fil_mode) {
+  if (plane_mode) {
     if (!pol_mode) {
       ec.fil_tscrunch = cfg.filterbank_tscrunch;
       ec.fil_fscrunch = cfg.filterbank_fscrunch;
@@ -557,6 +578,7 @@ int main(int argc, char** argv) {
     int buf_index;
     uint64_t counter;
     int pol_slot = -1;  // the combiner's slot (filterbank_polarization)
+    std::array<int, 2> incoh_slots{-1, -1};  // the searchers' slots
   };
   std::vector<InFlight> inflight;
   const size_t S = engine.n_channels(), Lw = engine.waterfall_len();
@@ -643,6 +665,56 @@ int main(int argc, char** argv) {
     if (udp_mode && n_endpoints > 1)
       SRTB_APP_LOGW("filterbank: several UDP endpoints share one file per "
                     "data stream");
+  }
+
+  // incoherent DM-offset search: one searcher and one candidates file per data
+  // stream; a searcher is fed right after its engine's submit and drained
+  // next to the filterbank rows
+  std::vector<std::unique_ptr<srtb_hip::IncoherentSearch>> searchers;
+  std::vector<FILE*> incoh_files;
+  double incoh_tsamp = 0.0;
+  uint64_t incoh_last_counter = 0, incoh_delta = 0;
+  bool incoh_have_last = false;
+  if (incoh_mode) {
+    const double bw = std::fabs(cfg.baseband_bandwidth);
+    const size_t C = engine.filterbank_channels();
+    srtb_hip::IncoherentSearchConfig ic;
+    ic.rows = engine.filterbank_rows();
+    ic.channels = C;
+    ic.foff = -bw / (double)C;
+    ic.fch1 = std::max(cfg.baseband_freq_low,
+                       cfg.baseband_freq_low + cfg.baseband_bandwidth) -
+              bw / (double)(2 * C);
+    ic.tsamp = 2.0 * (double)cfg.spectrum_channel_count *
+               (double)cfg.filterbank_tscrunch / cfg.baseband_sample_rate;
+    ic.offsets = cfg.incoherent_dm_offsets;
+    ic.snr_threshold = cfg.signal_detect_signal_noise_threshold;
+    ic.max_boxcar = cfg.signal_detect_max_boxcar_length;
+    incoh_tsamp = ic.tsamp;
+    for (int si = 0; si < n_streams; ++si) {
+      try {
+        searchers.emplace_back(
+            std::make_unique<srtb_hip::IncoherentSearch>(ic, 2));
+      } catch (const std::exception& e) {
+        SRTB_APP_LOGE("config: " << e.what());
+        return 2;
+      }
+      std::string tag;
+      if (n_streams > 1) tag += "_s" + std::to_string(si);
+      if (comm.world() > 1) tag += "_r" + std::to_string(comm.rank());
+      const std::string path =
+          tag_before_extension(cfg.incoherent_output_path, tag);
+      FILE* f = std::fopen(path.c_str(), "w");
+      if (!f) {
+        SRTB_APP_LOGE("cannot write " << path);
+        return 3;
+      }
+      incoh_files.push_back(f);
+      SRTB_APP_LOGI("incoherent search -> " << path << " ("
+                    << ic.offsets.size() << " offsets, D_max = "
+                    << searchers.back()->d_max() << " rows of " << ic.rows
+                    << " per block)");
+    }
   }
 
   // pulsar folding: the engines accumulate, a sub-integration is read, written
@@ -894,6 +966,21 @@ int main(int argc, char** argv) {
       if (pol_mode) combiner->wait(w.pol_slot);
     }
     ++blocks;
+    for (size_t si = 0; si < searchers.size(); ++si) {
+      // one line per (trial, length) with samples over the threshold: block
+      // ordinal, time of the peak (s from the start of the stream), dm +
+      // offset, boxcar length, snr; srtb_amd.main prints the same bytes
+      const srtb_hip::IncoherentResult r =
+          searchers[si]->wait(w.incoh_slots[si]);
+      for (const auto& tr : r.trials)
+        for (const auto& ln : tr.lengths)
+          if (ln.count > 0)
+            std::fprintf(incoh_files[si], "%" PRIu64 " %.9f %.6f %zu %.6f\n",
+                         r.block,
+                         (double)(r.first_row + (int64_t)ln.index) *
+                             incoh_tsamp,
+                         cfg.dm + tr.offset, ln.boxcar_length, ln.snr);
+    }
     if (fil_mode) {
       // copy the rows out of the slots' pinned mirrors now (the slots are
       // resubmitted next) and append them at this block's offset
@@ -1035,6 +1122,26 @@ int main(int argc, char** argv) {
     if (pol_mode)
       blk.pol_slot = combiner->submit(*engines[0], blk.slots[0], *engines[1],
                                       blk.slots[1]);
+    if (incoh_mode) {
+      // a UDP block that does not follow its predecessor at the usual step:
+      // rows are missing from the stream, the history starts over
+      if (incoh_have_last && msg.counter > incoh_last_counter) {
+        const uint64_t d = msg.counter - incoh_last_counter;
+        if (incoh_delta == 0) incoh_delta = d;
+        if (udp_mode && d != incoh_delta) {
+          SRTB_APP_LOGW("incoherent search: block " << msg.counter
+                        << " follows " << incoh_last_counter << " (step " << d
+                        << ", expected " << incoh_delta
+                        << "): data was dropped, the history restarts");
+          for (auto& s : searchers) s->reset();
+        }
+      }
+      incoh_last_counter = msg.counter;
+      incoh_have_last = true;
+      for (size_t si = 0; si < searchers.size(); ++si)
+        blk.incoh_slots[si] =
+            searchers[si]->submit(*engines[si], blk.slots[si]);
+    }
     inflight.push_back(blk);
     if (inflight.size() >= 2) drain_one();
   }
@@ -1050,6 +1157,7 @@ int main(int argc, char** argv) {
     writers.drain();
     for (const int fd : fil_fds) ::close(fd);
   }
+  for (FILE* f : incoh_files) std::fclose(f);
   stop.store(true);
   for (auto& t : input_threads)
     if (t.joinable()) t.join();

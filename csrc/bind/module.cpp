@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../engine/engine.h"
+#include "../engine/incoherent_search.h"
 #include "../engine/pol_combiner.h"
 #include "../fft/native_fft.h"
 #include "../include/srtb_kernels.h"
@@ -1372,6 +1373,188 @@ class PyPolCombiner {
   std::unique_ptr<PolCombiner> comb_;
 };
 
+// ---------------- incoherent DM-offset search bindings ----------------
+
+// Y float32 [T][R] of a linear window [D_max + R][C] and a table [T][C] int32
+torch::Tensor t_incoh_dedisperse(torch::Tensor window, torch::Tensor delays,
+                                 int64_t R) {
+  CHECK_CUDA(window);
+  CHECK_CUDA(delays);
+  CHECK_CONTIG(window);
+  CHECK_CONTIG(delays);
+  TORCH_CHECK(window.scalar_type() == torch::kFloat32 && window.dim() == 2,
+              "incoh_dedisperse: window must be float32 [D_max + R][C]");
+  TORCH_CHECK(delays.scalar_type() == torch::kInt32 && delays.dim() == 2,
+              "incoh_dedisperse: delays must be int32 [T][C]");
+  const int64_t rows = window.size(0), C = window.size(1), T = delays.size(0);
+  TORCH_CHECK(T >= 1 && T <= (int64_t)kIncohMaxTrials,
+              "incoh_dedisperse: needs 1 .. ", kIncohMaxTrials, " trials");
+  TORCH_CHECK(C >= 1 && delays.size(1) == C,
+              "incoh_dedisperse: window and delays differ in channels");
+  TORCH_CHECK(R >= (int64_t)kIncohMinRows && R <= rows,
+              "incoh_dedisperse: R must be ", kIncohMinRows,
+              " .. the window's ", rows, " rows");
+  const int64_t d_max = rows - R;
+  TORCH_CHECK(d_max <= (int64_t)kIncohMaxDelay &&
+                  (size_t)rows * (size_t)C * sizeof(float) <=
+                      kIncohMaxWindowBytes,
+              "incoh_dedisperse: the window exceeds the limits (D_max <= ",
+              kIncohMaxDelay, ", at most ", kIncohMaxWindowBytes, " bytes)");
+  // the kernel trusts the table: look at it here (one small reduction)
+  const int64_t lo = delays.min().item<int64_t>(),
+                hi = delays.max().item<int64_t>();
+  TORCH_CHECK(lo >= 0 && hi <= d_max, "incoh_dedisperse: delays must lie in ",
+              "0 .. ", d_max, ", found ", lo, " .. ", hi);
+  auto Y = torch::empty({T, R}, window.options());
+  torch::Tensor partials;
+  float* pp = nullptr;
+  if (const size_t np = incoh_partials(T, R, C)) {
+    partials = torch::empty({(int64_t)np}, window.options());
+    pp = partials.data_ptr<float>();
+  }
+  check(incoh_dedisperse(window.data_ptr<float>(), rows, 0,
+                         delays.data_ptr<int>(), T, R, C, pp,
+                         Y.data_ptr<float>(), cur_stream()),
+        "incoh_dedisperse");
+  return Y;
+}
+
+// (peak float64 [T][NL], index int64 [T][NL] (-1: no window), rms float64
+// [T][NL], count int64 [T][NL], mu float64 [T]) for lengths 1, 2, 4 ...
+// max_boxcar
+std::vector<torch::Tensor> t_incoh_detect(torch::Tensor Y, double snr,
+                                          int64_t max_boxcar) {
+  CHECK_CUDA(Y);
+  CHECK_CONTIG(Y);
+  TORCH_CHECK(Y.scalar_type() == torch::kFloat32 && Y.dim() == 2,
+              "incoh_detect: Y must be float32 [T][R]");
+  const int64_t T = Y.size(0), R = Y.size(1);
+  TORCH_CHECK(T >= 1 && T <= (int64_t)kIncohMaxTrials,
+              "incoh_detect: needs 1 .. ", kIncohMaxTrials, " trials");
+  TORCH_CHECK(R >= (int64_t)kIncohMinRows && R <= (int64_t)kIncohMaxRows,
+              "incoh_detect: R must be ", kIncohMinRows, " .. ",
+              kIncohMaxRows);
+  TORCH_CHECK(max_boxcar >= 1, "incoh_detect: max_boxcar must be >= 1");
+  const int nl = incoh_lengths((size_t)max_boxcar);
+  auto f64 = Y.options().dtype(torch::kFloat64);
+  auto i32 = Y.options().dtype(torch::kInt32);
+  auto peak = torch::empty({T, nl}, f64), rms = torch::empty({T, nl}, f64);
+  auto mu = torch::empty({T}, f64);
+  auto index = torch::empty({T, nl}, i32), count = torch::empty({T, nl}, i32);
+  check(incoh_detect(Y.data_ptr<float>(), T, R, nl, snr,
+                     peak.data_ptr<double>(),
+                     reinterpret_cast<unsigned*>(index.data_ptr<int>()),
+                     rms.data_ptr<double>(),
+                     reinterpret_cast<unsigned*>(count.data_ptr<int>()),
+                     mu.data_ptr<double>(), cur_stream()),
+        "incoh_detect");
+  // UINT_MAX reads as -1 through int32
+  return {peak, index.to(torch::kInt64), rms, count.to(torch::kInt64), mu};
+}
+
+class PyIncoherentSearch {
+ public:
+  PyIncoherentSearch(int64_t rows, int64_t channels, double fch1, double foff,
+                     double tsamp, std::vector<double> offsets,
+                     double snr_threshold, int64_t max_boxcar,
+                     int64_t n_slots) {
+    TORCH_CHECK(rows >= 0 && channels >= 0 && max_boxcar >= 0,
+                "IncoherentSearch: sizes must not be negative");
+    IncoherentSearchConfig c;
+    c.rows = (size_t)rows;
+    c.channels = (size_t)channels;
+    c.fch1 = fch1;
+    c.foff = foff;
+    c.tsamp = tsamp;
+    c.offsets = std::move(offsets);
+    c.snr_threshold = snr_threshold;
+    c.max_boxcar = (size_t)max_boxcar;
+    s_ = std::make_unique<IncoherentSearch>(c, (int)n_slots);
+    check(hipEventCreateWithFlags(&ev_, hipEventDisableTiming),
+          "incoherent producer event");
+  }
+  ~PyIncoherentSearch() {
+    s_.reset();
+    if (ev_) (void)hipEventDestroy(ev_);
+  }
+
+  int64_t submit(PyEngine& eng, int64_t slot) {
+    return s_->submit(eng.engine(), (int)slot);
+  }
+
+  // plane: float32 [R][C] on the GPU, produced on the current torch stream;
+  // it must stay alive and unchanged until wait(k)
+  int64_t submit_plane(torch::Tensor plane) {
+    CHECK_CUDA(plane);
+    CHECK_CONTIG(plane);
+    TORCH_CHECK(plane.scalar_type() == torch::kFloat32 && plane.dim() == 2 &&
+                    plane.size(0) == (int64_t)s_->rows() &&
+                    plane.size(1) == (int64_t)s_->channels(),
+                "IncoherentSearch: plane must be float32 [", s_->rows(), "][",
+                s_->channels(), "]");
+    check(hipEventRecord(ev_, cur_stream()), "incoherent producer record");
+    return s_->submit_plane(plane.data_ptr<float>(), ev_);
+  }
+
+  // {valid, first_row, block, trials: [{offset, mean, lengths:
+  // [{boxcar_length, peak, index, rms, count, snr}]}]}
+  py::dict wait(int64_t k) {
+    const IncoherentResult r = s_->wait((int)k);
+    py::dict d;
+    d["valid"] = r.valid;
+    d["first_row"] = r.first_row;
+    d["block"] = r.block;
+    py::list trials;
+    for (const IncoherentTrial& t : r.trials) {
+      py::dict td;
+      td["offset"] = t.offset;
+      td["mean"] = t.mean;
+      py::list ls;
+      for (const IncoherentDetection& l : t.lengths) {
+        py::dict ld;
+        ld["boxcar_length"] = l.boxcar_length;
+        ld["peak"] = l.peak;
+        ld["index"] = l.index == 0xFFFFFFFFu ? (int64_t)-1 : (int64_t)l.index;
+        ld["rms"] = l.rms;
+        ld["count"] = l.count;
+        ld["snr"] = l.snr;
+        ls.append(ld);
+      }
+      td["lengths"] = ls;
+      trials.append(td);
+    }
+    d["trials"] = trials;
+    return d;
+  }
+
+  // [T][R] float32: a copy of the slot's pinned mirror, complete after wait(k)
+  torch::Tensor plane(int64_t k) {
+    return torch::from_blob(const_cast<float*>(s_->plane_host((int)k)),
+                            {(int64_t)s_->trials(), (int64_t)s_->rows()},
+                            torch::TensorOptions().dtype(torch::kFloat32))
+        .clone();
+  }
+
+  // [T][C] int32 on the CPU
+  torch::Tensor delays() {
+    const auto& d = s_->delays();
+    return torch::from_blob(const_cast<int32_t*>(d.data()),
+                            {(int64_t)s_->trials(), (int64_t)s_->channels()},
+                            torch::TensorOptions().dtype(torch::kInt32))
+        .clone();
+  }
+
+  void reset() { s_->reset(); }
+  int64_t d_max() const { return (int64_t)s_->d_max(); }
+  int64_t rows() const { return (int64_t)s_->rows(); }
+  int64_t channels() const { return (int64_t)s_->channels(); }
+  int64_t trials() const { return (int64_t)s_->trials(); }
+
+ private:
+  std::unique_ptr<IncoherentSearch> s_;
+  hipEvent_t ev_ = nullptr;
+};
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1523,4 +1706,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property_readonly("rows", &PyPolCombiner::rows)
       .def_property_readonly("channels", &PyPolCombiner::channels)
       .def_property_readonly("nifs", &PyPolCombiner::nifs);
+
+  m.def("incoh_dedisperse", &t_incoh_dedisperse, py::arg("window"),
+        py::arg("delays"), py::arg("R"));
+  m.def("incoh_detect", &t_incoh_detect, py::arg("Y"), py::arg("snr"),
+        py::arg("max_boxcar"));
+  m.attr("INCOH_CHANNEL_CHUNK") = (int64_t)kIncohChannelChunk;
+  m.attr("INCOH_MAX_ROWS") = (int64_t)kIncohMaxRows;
+  py::class_<PyIncoherentSearch>(m, "IncoherentSearch")
+      .def(py::init<int64_t, int64_t, double, double, double,
+                    std::vector<double>, double, int64_t, int64_t>(),
+           py::arg("rows"), py::arg("channels"), py::arg("fch1"),
+           py::arg("foff"), py::arg("tsamp"), py::arg("offsets"),
+           py::arg("snr_threshold"), py::arg("max_boxcar"),
+           py::arg("n_slots") = 2)
+      .def("submit", &PyIncoherentSearch::submit, py::arg("engine"),
+           py::arg("slot"))
+      .def("submit_plane", &PyIncoherentSearch::submit_plane, py::arg("plane"))
+      .def("wait", &PyIncoherentSearch::wait)
+      .def("plane", &PyIncoherentSearch::plane)
+      .def("delays", &PyIncoherentSearch::delays)
+      .def("reset", &PyIncoherentSearch::reset)
+      .def_property_readonly("d_max", &PyIncoherentSearch::d_max)
+      .def_property_readonly("rows", &PyIncoherentSearch::rows)
+      .def_property_readonly("channels", &PyIncoherentSearch::channels)
+      .def_property_readonly("trials", &PyIncoherentSearch::trials);
 }

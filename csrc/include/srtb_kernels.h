@@ -304,6 +304,50 @@ hipError_t fold_block(const float2* wf, const uint8_t* flags, size_t S,
                       uint32_t* table, double* acc, uint64_t* hits,
                       uint64_t* weights, hipStream_t stream);
 
+// ---------------- incoherent DM-offset search (csrc/kernels/incoherent.hip) --
+// Definition: docs/ARCHITECTURE.md, "Incoherent DM-offset search".
+constexpr size_t kIncohMaxTrials = 1024;
+constexpr size_t kIncohMinRows = 2;
+// incoh_detect keeps a trial's fp64 scan in LDS, one workgroup per trial:
+// 16384 rows * 8 bytes = 128 KiB of the 160 KiB of a gfx950 CU
+constexpr size_t kIncohMaxRows = 16384;
+constexpr size_t kIncohMaxDelay = (size_t)1 << 20;  // D_max, rows
+// (D_max + R) * C * 4 bytes of history; 1 GiB is 64 full-size planes
+// (R = 16384, C = 4096) and far below what the engine itself allocates
+constexpr size_t kIncohMaxWindowBytes = (size_t)1 << 30;
+constexpr size_t kIncohChannelChunk = 1024;  // channels per partial sum
+constexpr int kIncohMaxLengths = 21;  // boxcar lengths 1, 2, 4 ... 2^20
+
+// Y[t][j] = sum_c W[j + delays[t][c]][c] in fp32, t < T, j < R, where row w
+// of the window W is row (row0 + w) mod ring_rows of `window`
+// ([ring_rows][C] floats, ring_rows >= R; a linear window is row0 = 0).
+// delays: [T][C] int32 with every entry in 0 .. ring_rows - R, which the
+// caller guarantees (the kernel does not check).  Channels are summed in
+// chunks of kIncohChannelChunk; with more than one chunk, `partials` must hold
+// incoh_partials(T, R, C) floats (else it may be null).  The order of
+// summation depends on C and the launch constants only; no atomics,
+// bit-identical from run to run.  Geometry outside the limits above returns
+// hipErrorInvalidValue and launches nothing.
+int incoh_chunks(size_t C);
+size_t incoh_partials(size_t T, size_t R, size_t C);
+hipError_t incoh_dedisperse(const float* window, size_t ring_rows, size_t row0,
+                            const int* delays, size_t T, size_t R, size_t C,
+                            float* partials, float* Y, hipStream_t stream);
+
+// Detection on every row of Y[T][R] in one launch, fp64 throughout, for the
+// n_lengths boxcar lengths 1, 2, 4 ... (incoh_lengths(max_boxcar) of them):
+// mu[t] = mean of the row, z = Y - mu, cs = inclusive scan of z; length 1 is
+// z itself (n = R values), length l >= 2 is cs[i + l] - cs[i], i + l < R.
+// Per (t, length), [T][n_lengths]: peak and the lowest index attaining it,
+// rms = sqrt(sum b^2 / n), count = #{b > snr * rms}.  A length >= R has no
+// window: peak -infinity, index UINT_MAX, rms 0, count 0.
+// kIncohMinRows <= R <= kIncohMaxRows.
+int incoh_lengths(size_t max_boxcar);
+hipError_t incoh_detect(const float* Y, size_t T, size_t R, int n_lengths,
+                        double snr, double* out_peak, unsigned* out_index,
+                        double* out_rms, unsigned* out_count, double* out_mu,
+                        hipStream_t stream);
+
 // ---------------- hand-written Stockham FFT ----------------
 // One generic pass of the LDS-staged Stockham FFT (csrc/kernels/fft.hip).
 // Index-math oracle: srtb_amd/fftref.py.  Host-side planning:

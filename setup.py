@@ -30,8 +30,10 @@ HIP_SOURCES = [
     "csrc/kernels/fft.hip",
     "csrc/kernels/filterbank.hip",
     "csrc/kernels/fold.hip",
+    "csrc/kernels/incoherent.hip",
     "csrc/engine/engine.cpp",
     "csrc/engine/pol_combiner.cpp",
+    "csrc/engine/incoherent_search.cpp",
 ]
 
 HIPCC_FLAGS = [
@@ -55,6 +57,7 @@ def build_hip_objects():
                 os.path.join(ROOT, "csrc/kernels/common.h"),
                 os.path.join(ROOT, "csrc/engine/engine.h"),
                 os.path.join(ROOT, "csrc/engine/pol_combiner.h"),
+                os.path.join(ROOT, "csrc/engine/incoherent_search.h"),
                 os.path.join(ROOT, "csrc/fft/fft_plans.h"),
                 os.path.join(ROOT, "csrc/fft/native_fft.h")]
         if os.path.exists(obj) and all(
@@ -89,6 +92,7 @@ def build_apps(objects):
                 "csrc/app/pipe.h",
                 "csrc/app/udp_receiver.h", "csrc/app/writers.h",
                 "csrc/engine/engine.h", "csrc/engine/pol_combiner.h",
+                "csrc/engine/incoherent_search.h",
                 "csrc/fft/native_fft.h")]
         if os.path.exists(out) and all(
                 os.path.getmtime(out) >= os.path.getmtime(d) for d in deps

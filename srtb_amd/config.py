@@ -67,6 +67,8 @@ _FIELD_KINDS = {
     "fold_nbin": "int",
     "fold_phase_offset": "real",
     "fold_subint_blocks": "int",
+    "incoherent_dm_offsets": "reallist",
+    "incoherent_output_path": "str",
 }
 
 
@@ -130,6 +132,11 @@ class Config:
     fold_nbin: int = 256
     fold_phase_offset: float = 0.0
     fold_subint_blocks: int = 0
+    # incoherent DM-offset search on the filterbank plane: offsets in pc cm^-3
+    # around dm, comma-separated expressions ("" = off), and the candidates
+    # text file
+    incoherent_dm_offsets: str = ""
+    incoherent_output_path: str = ""
 
     # ---- assignment from strings (expression values) ----
 
@@ -183,6 +190,10 @@ class Config:
     def dm_trials(self) -> List[float]:
         """The trial DMs of ``dm_trial_list`` ([] when the key is unset)."""
         return _parse_real_list(self.dm_trial_list)
+
+    def incoherent_offsets(self) -> List[float]:
+        """The offsets of ``incoherent_dm_offsets`` ([] when the key is unset)."""
+        return _parse_real_list(self.incoherent_dm_offsets)
 
     def fold_spin(self) -> tuple:
         """(f0 in Hz, f1 in Hz/s) of ``fold_period`` / ``fold_period_derivative``:

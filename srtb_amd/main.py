@@ -51,10 +51,17 @@ def write_ppm(path: str, argb: np.ndarray) -> None:
         f.write(rgb.tobytes())
 
 
+def filterbank_plane_on(cfg: Config) -> bool:
+    """Whether the blocks build the filterbank power plane: for the file, for
+    the incoherent DM-offset search, or for both."""
+    return bool(cfg.filterbank_output_path
+                or cfg.incoherent_dm_offsets.strip())
+
+
 def filterbank_time_multiple(cfg: Config) -> int:
     """The overlap's extra rounding factor: tscrunch while the filterbank
-    output is on, so a block's valid waterfall columns are whole output rows."""
-    return cfg.filterbank_tscrunch if cfg.filterbank_output_path else 1
+    plane is on, so a block's valid waterfall columns are whole output rows."""
+    return cfg.filterbank_tscrunch if filterbank_plane_on(cfg) else 1
 
 
 def filterbank_paths(cfg: Config, n_streams: int, rank: int, world: int,
@@ -106,6 +113,86 @@ def check_filterbank_polarization(cfg: Config, n_streams: int) -> None:
             "other (a filterbank file holds one DM)")
 
 
+def check_incoherent_config(cfg: Config) -> None:
+    """Reject an incoherent_dm_offsets the run cannot honour."""
+    if not cfg.incoherent_dm_offsets.strip():
+        if cfg.incoherent_output_path:
+            raise SystemExit(
+                "config: incoherent_output_path needs incoherent_dm_offsets")
+        return
+    if not cfg.incoherent_output_path:
+        raise SystemExit(
+            "config: incoherent_dm_offsets needs incoherent_output_path")
+    if cfg.dm_trial_list.strip():
+        raise SystemExit(
+            "config: incoherent_dm_offsets and dm_trial_list exclude each "
+            "other (the offsets are searched around the one coherent dm)")
+    if cfg.filterbank_polarization:
+        raise SystemExit(
+            "config: incoherent_dm_offsets and filterbank_polarization "
+            "exclude each other (the search runs on per-stream planes)")
+
+
+def incoherent_paths(cfg: Config, n_streams: int, rank: int, world: int,
+                     endpoint: int | None = None) -> list[str]:
+    """One candidates file per data stream, tagged like the filterbank's."""
+    fil = cfg.copy()
+    fil.filterbank_output_path = cfg.incoherent_output_path
+    return filterbank_paths(fil, n_streams, rank, world, endpoint)
+
+
+class IncoherentOutput:
+    """The searchers of one pipeline (one per data stream) and their
+    candidates files.  On the GPU a searcher consumes the engine slot's power
+    plane on its own stream; on the CPU it is ref.CpuIncoherentSearch fed with
+    the oracle plane."""
+
+    def __init__(self, cfg: Config, paths: list[str], rows: int,
+                 native=None):
+        hdr = ref.filterbank_header_fields(
+            cfg.baseband_freq_low, cfg.baseband_bandwidth,
+            cfg.baseband_sample_rate, cfg.spectrum_channel_count,
+            cfg.filterbank_tscrunch, cfg.filterbank_fscrunch)
+        self.cfg, self.tsamp = cfg, hdr["tsamp"]
+        self.native = native
+        kw = dict(fch1=hdr["fch1"], foff=hdr["foff"], tsamp=hdr["tsamp"],
+                  offsets=cfg.incoherent_offsets(),
+                  snr_threshold=cfg.signal_detect_signal_noise_threshold,
+                  max_boxcar=cfg.signal_detect_max_boxcar_length)
+        try:
+            if native is not None:
+                self.searchers = [native.IncoherentSearch(
+                    rows=rows, channels=hdr["nchans"], **kw) for _ in paths]
+            else:
+                self.searchers = [ref.CpuIncoherentSearch(
+                    rows, hdr["nchans"], **kw) for _ in paths]
+        except (RuntimeError, ValueError) as e:
+            raise SystemExit(f"config: {e}")
+        self.files = [open(p_, "w") for p_ in paths]
+
+    def block_done(self, pipe) -> None:
+        if self.native is not None:
+            engines = getattr(pipe, "engines", None) or [pipe.eng]
+            slots = getattr(pipe, "last_slots", None) or [pipe.last_slot]
+            ks = [s.submit(e, sl)
+                  for s, e, sl in zip(self.searchers, engines, slots)]
+            results = [s.wait(k) for s, k in zip(self.searchers, ks)]
+        else:
+            results = [s.add(plane) for s, plane in
+                       zip(self.searchers, pipe.filterbank_power_blocks())]
+        for f, res in zip(self.files, results):
+            f.writelines(ref.incoherent_candidate_lines(
+                res, self.tsamp, self.cfg.dm))
+
+    def reset(self) -> None:
+        for s in self.searchers:
+            s.reset()
+
+    def close(self) -> None:
+        for f in self.files:
+            f.close()
+
+
 def cpu_pol_filterbank_block(cfg: Config, results: list,
                              nsamps_reserved: int) -> np.ndarray:
     """The combiner's [R][P][C] rows of one block from the oracle functions
@@ -126,15 +213,21 @@ def cpu_pol_filterbank_block(cfg: Config, results: list,
     return ref.filterbank_quantize(flat, mean, std).reshape(plane.shape)
 
 
+def cpu_filterbank_power(cfg: Config, wf: np.ndarray,
+                         nsamps_reserved: int) -> np.ndarray:
+    """The float32 power plane [R][C] of one block from the oracle."""
+    valid = ref.filterbank_valid_rows(cfg.baseband_input_count, wf.shape[0],
+                                      nsamps_reserved)
+    return ref.filterbank_block(
+        wf, valid, cfg.filterbank_tscrunch, cfg.filterbank_fscrunch,
+        reverse=cfg.baseband_bandwidth > 0).astype(np.float32)
+
+
 def cpu_filterbank_block(cfg: Config, wf: np.ndarray,
                          nsamps_reserved: int) -> np.ndarray:
     """The engine's filterbank rows of one block from the oracle functions
     (wf: the SK-zapped waterfall)."""
-    valid = ref.filterbank_valid_rows(cfg.baseband_input_count, wf.shape[0],
-                                      nsamps_reserved)
-    power = ref.filterbank_block(
-        wf, valid, cfg.filterbank_tscrunch, cfg.filterbank_fscrunch,
-        reverse=cfg.baseband_bandwidth > 0).astype(np.float32)
+    power = cpu_filterbank_power(cfg, wf, nsamps_reserved)
     if cfg.filterbank_nbits == 32:
         return power
     mean, std = ref.filterbank_channel_stats(power)
@@ -465,6 +558,11 @@ class CpuMultiPolPipeline:
                                      self.nsamps_reserved)
                 for r in self.last_results]
 
+    def filterbank_power_blocks(self) -> list[np.ndarray]:
+        return [cpu_filterbank_power(self.cfg, r["waterfall"],
+                                     self.nsamps_reserved)
+                for r in self.last_results]
+
     def _fanout(self, raw: np.ndarray) -> list[np.ndarray]:
         if self.fmt == "gznupsr_a1":
             return ref.unpack_gznupsr_a1(raw, self.n_streams)
@@ -533,6 +631,10 @@ class CpuStreamPipeline:
         return [cpu_filterbank_block(self.cfg, self.last_result["waterfall"],
                                      self.nsamps_reserved)]
 
+    def filterbank_power_blocks(self) -> list[np.ndarray]:
+        return [cpu_filterbank_power(self.cfg, self.last_result["waterfall"],
+                                     self.nsamps_reserved)]
+
     def process_block(self, raw: np.ndarray, counter: int) -> BlockProducts:
         cfg = self.cfg
         res = self.pipe.process_block(raw)
@@ -594,7 +696,8 @@ def main(argv=None) -> int:
     cfg = parse_args(cfg_argv) if rank == 0 else Config()
     cfg = broadcast_config(cfg if rank == 0 else None)
 
-    if cfg.filterbank_output_path:
+    check_incoherent_config(cfg)
+    if filterbank_plane_on(cfg):
         if cfg.dm_trial_list.strip():
             raise SystemExit(
                 "config: filterbank_output_path and dm_trial_list exclude each "
@@ -695,7 +798,7 @@ def main(argv=None) -> int:
                 rows = rows[:, 0, :]  # polarization state I: [R][1][C]
             w.append(rows)
 
-    if cfg.filterbank_output_path:
+    if filterbank_plane_on(cfg):
         valid = cfg.baseband_input_count - reserved
         per = 2 * cfg.spectrum_channel_count * cfg.filterbank_tscrunch
         if valid <= 0 or valid % per:
@@ -703,6 +806,27 @@ def main(argv=None) -> int:
                 f"config: baseband_input_count - overlap = {valid} is not a "
                 f"positive multiple of 2 * spectrum_channel_count * "
                 f"filterbank_tscrunch = {per}")
+
+    # incoherent DM-offset search: one IncoherentOutput per pipeline (per
+    # endpoint in UDP mode), one searcher and candidates file per data stream
+    incoh_on = bool(cfg.incoherent_dm_offsets.strip())
+    incoh_outs: dict = {}
+
+    def incoh_block_done(pipe, ep=None, n_eps=1, dropped=False):
+        if ep not in incoh_outs:
+            rows = ((cfg.baseband_input_count - reserved)
+                    // (2 * cfg.spectrum_channel_count
+                        * cfg.filterbank_tscrunch))
+            incoh_outs[ep] = IncoherentOutput(
+                cfg, incoherent_paths(cfg, n_streams, rank, world,
+                                      endpoint=ep if n_eps > 1 else None),
+                rows, native=getattr(pipe, "C", None))
+        if dropped:
+            print(f"[srtb_amd] incoherent search: data was dropped before "
+                  f"this block{'' if ep is None else f' of endpoint {ep}'}; "
+                  f"the history restarts")
+            incoh_outs[ep].reset()
+        incoh_outs[ep].block_done(pipe)
 
     # pulsar folding: one FoldOutput per pipeline (per endpoint in UDP mode)
     fold_outs: dict = {}
@@ -747,6 +871,8 @@ def main(argv=None) -> int:
             for products in process(pipe, raw, sample_index):
                 writer.push(products)
             fil_append(pipe)
+            if incoh_on:
+                incoh_block_done(pipe)
             if fold_on:
                 fold_block_done(pipe, sample_index // n_streams)
             if write_all_f is not None:
@@ -825,6 +951,17 @@ def main(argv=None) -> int:
                       f"block {ts}; the phase follows the packet counter")
             return n0
 
+        # a block whose begin counter does not follow its predecessor's (for
+        # formats that carry one): data was dropped in between
+        incoh_last: dict = {}
+
+        def udp_dropped(ep, ts):
+            last = incoh_last.get(ep)
+            incoh_last[ep] = ts
+            if not per_packet or last is None:
+                return False
+            return (ts - last) * per_packet != cfg.baseband_input_count
+
         threads = [threading.Thread(target=receiver, args=(ep,), daemon=True)
                    for ep in my]
         for t in threads:
@@ -840,6 +977,9 @@ def main(argv=None) -> int:
             for products in process(pipes[ep], blk, ts):
                 writer.push(products)
             fil_append(pipes[ep], ep, len(my))
+            if incoh_on:
+                incoh_block_done(pipes[ep], ep, len(my),
+                                 dropped=udp_dropped(ep, ts))
             if fold_on:
                 fold_block_done(pipes[ep], n0, ep, len(my))
             state["n"] += 1
@@ -852,6 +992,8 @@ def main(argv=None) -> int:
     for ws in fil_writers.values():
         for w in ws:
             w.close()
+    for out in incoh_outs.values():
+        out.close()
     for ep, out in fold_outs.items():
         out.flush(pipe if cfg.input_file_path else pipes[ep])
     elapsed = time.time() - t0

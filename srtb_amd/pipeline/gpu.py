@@ -22,10 +22,12 @@ from ..config import Config
 
 
 def filterbank_engine_kwargs(cfg: Config) -> dict:
-    """Engine keywords that switch the per-stream filterbank output on ({}
-    while ``filterbank_output_path`` is unset, and with
-    ``filterbank_polarization``, where a PolCombiner makes the one plane)."""
-    if not cfg.filterbank_output_path or cfg.filterbank_polarization:
+    """Engine keywords that switch the per-stream filterbank plane on ({}
+    while neither ``filterbank_output_path`` nor ``incoherent_dm_offsets`` is
+    set, and with ``filterbank_polarization``, where a PolCombiner makes the
+    one plane)."""
+    plane = cfg.filterbank_output_path or cfg.incoherent_dm_offsets.strip()
+    if not plane or cfg.filterbank_polarization:
         return {}
     return {"fil_tscrunch": cfg.filterbank_tscrunch,
             "fil_fscrunch": cfg.filterbank_fscrunch,

@@ -694,6 +694,213 @@ class CpuFolder:
 
 
 # ---------------------------------------------------------------------------
+# Incoherent DM-offset search on the filterbank power plane (no reference
+# counterpart; definition in docs/ARCHITECTURE.md, "Incoherent DM-offset
+# search")
+# ---------------------------------------------------------------------------
+
+INCOH_MAX_TRIALS = 1024
+INCOH_MIN_ROWS = 2
+INCOH_MAX_ROWS = 16384
+INCOH_MAX_DELAY = 1 << 20
+INCOH_MAX_WINDOW_BYTES = 1 << 30
+INCOH_MAX_LENGTHS = 21
+
+
+def incoherent_delays(fch1: float, foff: float, C: int, tsamp: float,
+                      offsets) -> np.ndarray:
+    """Delay table d[t][c] (int32, rows of the plane, all >= 0) of the offsets
+    delta_t in pc cm^-3.  delta >= 0 delays channel c against channel 0 (the
+    top of the band), delta < 0 against channel C - 1 (the bottom):
+      delta >= 0: rint(D * delta   * (f(c)^-2     - f(0)^-2) / tsamp)
+      delta <  0: rint(D * |delta| * (f(C-1)^-2   - f(c)^-2) / tsamp)
+    with f(c) = fch1 + c * foff in MHz, every operation rounded in fp64 in the
+    order written (the native table is the same bit for bit)."""
+    offsets = np.atleast_1d(np.asarray(offsets, dtype=np.float64))
+    if C < 1 or not tsamp > 0 or not np.all(np.isfinite(offsets)):
+        raise ValueError("incoherent_delays: needs channels >= 1, tsamp > 0 "
+                         "and finite offsets")
+    f = np.float64(fch1) + np.arange(C, dtype=np.float64) * np.float64(foff)
+    if not np.all(f > 0):
+        raise ValueError("incoherent_delays: every channel centre must be "
+                         "> 0 MHz")
+    inv2 = 1.0 / (f * f)
+    d = np.empty((offsets.size, C), dtype=np.float64)
+    for t, delta in enumerate(offsets):
+        diff = inv2 - inv2[0] if delta >= 0 else inv2[C - 1] - inv2
+        d[t] = np.rint(D_DISPERSION * abs(delta) * diff / np.float64(tsamp))
+    if d.size and (d.min() < 0 or d.max() > INCOH_MAX_DELAY):
+        raise ValueError(f"incoherent_delays: delays of {d.min():.0f} .. "
+                         f"{d.max():.0f} rows are outside 0 .. "
+                         f"{INCOH_MAX_DELAY}")
+    return d.astype(np.int32)
+
+
+def incoherent_dedisperse(window: np.ndarray, delays: np.ndarray,
+                          R: int) -> np.ndarray:
+    """Y[t][j] = sum_c window[j + delays[t][c]][c], j < R, in float64.
+    window: [D + R][C] with every delay in 0 .. D."""
+    window = np.asarray(window, dtype=np.float64)
+    delays = np.asarray(delays)
+    T, C = delays.shape
+    if window.ndim != 2 or window.shape[1] != C or not 1 <= R <= len(window):
+        raise ValueError("incoherent_dedisperse: bad geometry")
+    if delays.min() < 0 or delays.max() > len(window) - R:
+        raise ValueError("incoherent_dedisperse: a delay is outside the window")
+    rows = np.arange(R)[:, None]
+    cols = np.arange(C)[None, :]
+    Y = np.empty((T, R), dtype=np.float64)
+    for t in range(T):
+        Y[t] = window[rows + delays[t][None, :], cols].sum(axis=1)
+    return Y
+
+
+def incoherent_lengths(max_boxcar: int) -> list[int]:
+    """Boxcar lengths 1, 2, 4 ... <= max_boxcar (at most INCOH_MAX_LENGTHS)."""
+    out, l = [], 1
+    while l <= max_boxcar and len(out) < INCOH_MAX_LENGTHS:
+        out.append(l)
+        l *= 2
+    return out
+
+
+def incoherent_series(y: np.ndarray, length: int) -> tuple[float, np.ndarray]:
+    """(mu, b_l) of one row: z = y - mu; length 1 is z itself, length l >= 2
+    is cs[i + l] - cs[i], i + l < R, cs the inclusive scan of z.  Empty where
+    the length has no window."""
+    y = np.asarray(y, dtype=np.float64)
+    mu = y.sum() / y.size
+    z = y - mu
+    if length == 1:
+        return mu, z
+    cs = np.cumsum(z)
+    n = max(y.size - length, 0)
+    return mu, cs[length:length + n] - cs[:n]
+
+
+def incoherent_detect(Y: np.ndarray, snr: float, max_boxcar: int) -> dict:
+    """Per trial (row of Y) and boxcar length, all float64: 'peak' and 'index'
+    (lowest index attaining it), 'rms' = sqrt(sum b^2 / n), 'count' = #{b > snr
+    * rms}, 'snr' = peak / rms (0 where rms = 0), each [T][NL]; 'mu' [T];
+    'lengths'.  A length without a window has peak -inf, index -1, rms 0,
+    count 0."""
+    Y = np.asarray(Y, dtype=np.float64)
+    T, R = Y.shape
+    lengths = incoherent_lengths(max_boxcar)
+    NL = len(lengths)
+    out = {
+        "lengths": lengths,
+        "peak": np.full((T, NL), -np.inf),
+        "index": np.full((T, NL), -1, dtype=np.int64),
+        "rms": np.zeros((T, NL)),
+        "count": np.zeros((T, NL), dtype=np.int64),
+        "snr": np.zeros((T, NL)),
+        "mu": np.zeros(T),
+    }
+    for t in range(T):
+        for k, l in enumerate(lengths):
+            mu, b = incoherent_series(Y[t], l)
+            out["mu"][t] = mu
+            if b.size == 0:
+                continue
+            rms = np.sqrt((b * b).sum() / b.size)
+            i = int(np.argmax(b))  # first occurrence
+            out["peak"][t, k] = b[i]
+            out["index"][t, k] = i
+            out["rms"][t, k] = rms
+            out["count"][t, k] = int((b > snr * rms).sum())
+            out["snr"][t, k] = b[i] / rms if rms > 0 else 0.0
+    return out
+
+
+def incoherent_result_trials(det: dict, offsets) -> list[dict]:
+    """The detect arrays in the per-trial form IncoherentSearch.wait returns."""
+    trials = []
+    for t, delta in enumerate(offsets):
+        trials.append({
+            "offset": float(delta), "mean": float(det["mu"][t]),
+            "lengths": [{
+                "boxcar_length": int(l), "peak": float(det["peak"][t, k]),
+                "index": int(det["index"][t, k]),
+                "rms": float(det["rms"][t, k]),
+                "count": int(det["count"][t, k]),
+                "snr": float(det["snr"][t, k]),
+            } for k, l in enumerate(det["lengths"])]})
+    return trials
+
+
+class CpuIncoherentSearch:
+    """Streaming search with the history, priming and result semantics of the
+    native IncoherentSearch: block b's output row j stands for global row
+    b * R - D_max + j, rows before the stream are zero, and a block is valid
+    (and searched) iff b * R >= D_max."""
+
+    def __init__(self, R: int, C: int, fch1: float, foff: float, tsamp: float,
+                 offsets, snr_threshold: float, max_boxcar: int):
+        self.offsets = [float(x) for x in np.atleast_1d(offsets)]
+        if not 1 <= len(self.offsets) <= INCOH_MAX_TRIALS:
+            raise ValueError(f"incoherent search: needs 1 .. "
+                             f"{INCOH_MAX_TRIALS} offsets")
+        if not INCOH_MIN_ROWS <= R <= INCOH_MAX_ROWS:
+            raise ValueError(f"incoherent search: rows per block must be "
+                             f"{INCOH_MIN_ROWS} .. {INCOH_MAX_ROWS}")
+        if C < 1 or max_boxcar < 1:
+            raise ValueError("incoherent search: needs channels >= 1 and "
+                             "max_boxcar >= 1")
+        self.R, self.C = int(R), int(C)
+        self.snr_threshold, self.max_boxcar = float(snr_threshold), max_boxcar
+        self.delays = incoherent_delays(fch1, foff, C, tsamp, self.offsets)
+        self.d_max = int(self.delays.max())
+        if (self.d_max + R) * C * 4 > INCOH_MAX_WINDOW_BYTES:
+            raise ValueError(
+                f"incoherent search: the history of (D_max + R) * C * 4 bytes "
+                f"(D_max = {self.d_max} rows) exceeds the cap of "
+                f"{INCOH_MAX_WINDOW_BYTES}")
+        self.reset()
+
+    def reset(self) -> None:
+        self.window = np.zeros((self.d_max + self.R, self.C), dtype=np.float64)
+        self.block = 0
+
+    def add(self, plane: np.ndarray) -> dict:
+        """One block's [R][C] plane -> {'valid', 'first_row', 'block', 'Y'
+        (float64 [T][R]), 'trials' (empty unless valid)}."""
+        plane = np.asarray(plane, dtype=np.float64)
+        if plane.shape != (self.R, self.C):
+            raise ValueError("incoherent search: plane shape differs")
+        self.window = np.concatenate([self.window[self.R:], plane])
+        b = self.block
+        self.block += 1
+        Y = incoherent_dedisperse(self.window, self.delays, self.R)
+        valid = b * self.R >= self.d_max
+        trials = []
+        if valid:
+            trials = incoherent_result_trials(
+                incoherent_detect(Y, self.snr_threshold, self.max_boxcar),
+                self.offsets)
+        return {"valid": valid, "first_row": b * self.R - self.d_max,
+                "block": b, "Y": Y, "trials": trials}
+
+
+def incoherent_candidate_lines(result: dict, tsamp: float, dm: float) -> list[str]:
+    """Candidate lines of one valid block's result, one per (trial, length)
+    with count > 0: block ordinal, time of the peak in seconds from the start
+    of the stream ((first_row + index) * tsamp), dm + delta, boxcar length,
+    snr.  The native backend prints the same bytes."""
+    lines = []
+    if not result["valid"]:
+        return lines
+    for tr in result["trials"]:
+        for ln in tr["lengths"]:
+            if ln["count"] > 0:
+                time_s = (result["first_row"] + ln["index"]) * tsamp
+                lines.append("%d %.9f %.6f %d %.6f\n" % (
+                    result["block"], time_s, dm + tr["offset"],
+                    ln["boxcar_length"], ln["snr"]))
+    return lines
+
+
+# ---------------------------------------------------------------------------
 # Spectrum simplification for display
 # (reference: spectrum/simplify_spectrum.hpp:37-731)
 # ---------------------------------------------------------------------------
