@@ -21,6 +21,14 @@ fscrunch 1 makes it the plane's C as well (4096 by default).
            python benchmarks/incoherent_bench.py --mode kernels
      (k_incoh_dedisperse, k_incoh_combine and k_incoh_detect run once per
      block each).
+  --mode search
+     The searcher alone: runs of --blocks blocks of submit_plane on a fixed
+     plane (two in flight), --repeats of them, each timed by the host clock
+     around work that ends in the last wait.  With --normalize the runs
+     alternate between a searcher without the per-channel normalisation and
+     one with it (--normalize-blocks), in the same process; it reports ms per
+     block per run, the medians, the spread (max - min) of the repeats and
+     the on - off cost with its share of the off block time.
 
 Prints one JSON line.
 """
@@ -39,7 +47,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("wall", "kernels"), default="wall")
+    ap.add_argument("--mode", choices=("wall", "kernels", "search"),
+                    default="wall")
+    ap.add_argument("--normalize", action="store_true",
+                    help="--mode search: alternate normalisation off and on")
+    ap.add_argument("--normalize-blocks", type=int, default=8)
     ap.add_argument("--n", type=int, default=2**30)
     ap.add_argument("--channels", type=int, default=2**12)
     ap.add_argument("--blocks", type=int, default=24)
@@ -70,10 +82,11 @@ def main(argv=None):
                                        args.tscrunch, 1)
     rows = (n - reserved) // (2 * s * args.tscrunch)
     offsets = np.linspace(-args.span, args.span, args.trials).tolist()
-    search = C.IncoherentSearch(
+    search_kw = dict(
         rows=rows, channels=hdr["nchans"], fch1=hdr["fch1"], foff=hdr["foff"],
         tsamp=hdr["tsamp"], offsets=offsets, snr_threshold=8.0,
         max_boxcar=args.max_boxcar)
+    search = C.IncoherentSearch(**search_kw)
     shape = {"n": n, "channels": s, "nsamps_reserved": reserved,
              "tscrunch": args.tscrunch, "rows": rows,
              "out_channels": hdr["nchans"], "trials": args.trials,
@@ -94,6 +107,50 @@ def main(argv=None):
         torch.cuda.synchronize()
         print(json.dumps({"shape": shape, "mode": "kernels",
                           "blocks": args.blocks}), flush=True)
+        return
+
+    if args.mode == "search":
+        plane = torch.from_numpy(rng.chisquare(
+            32, (rows, hdr["nchans"])).astype(np.float32)).cuda()
+        searchers = {"off": search}
+        if args.normalize:
+            searchers["on"] = C.IncoherentSearch(
+                normalize=True, normalize_blocks=args.normalize_blocks,
+                **search_kw)
+
+        def run_search(s, blocks):
+            pending = []
+            for _ in range(blocks):
+                pending.append(s.submit_plane(plane))
+                if len(pending) >= 2:
+                    s.wait(pending.pop(0))
+            for k in pending:
+                s.wait(k)
+
+        for s_ in searchers.values():  # warm-up
+            run_search(s_, 4)
+        ms = {name: [] for name in searchers}
+        for _ in range(args.repeats):
+            for name, s_ in searchers.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run_search(s_, args.blocks)
+                ms[name].append(
+                    (time.perf_counter() - t0) / args.blocks * 1e3)
+        out = {"shape": shape, "mode": "search",
+               "blocks_per_run": args.blocks}
+        for name, v in ms.items():
+            out[f"ms_per_block_{name}"] = [round(x, 4) for x in v]
+            out[f"median_{name}_ms"] = round(statistics.median(v), 4)
+            out[f"spread_{name}_ms"] = round(max(v) - min(v), 4)
+        if args.normalize:
+            extra = out["median_on_ms"] - out["median_off_ms"]
+            out["normalize_blocks"] = args.normalize_blocks
+            out["normalize_extra_ms_per_block"] = round(extra, 4)
+            out["normalize_share_of_off"] = round(
+                extra / out["median_off_ms"], 4)
+            out["plane_bytes"] = rows * hdr["nchans"] * 4
+        print(json.dumps(out), flush=True)
         return
 
     nc = n // 2

@@ -217,6 +217,10 @@ struct Config {
   // around dm (empty = off) and the candidates text file
   std::vector<double> incoherent_dm_offsets;
   std::string incoherent_output_path;
+  // per-channel normalisation of the rows before they are summed: off / on,
+  // and the blocks (1 .. 65536) the running mean and deviation average over
+  bool incoherent_normalize = false;
+  size_t incoherent_normalize_blocks = 8;
   // pulsar folding ("" = off), twin of the Python keys: period (s), its
   // derivative (s/s), phase bins, phase (turns) at stream sample 0, blocks
   // per sub-integration (0 = one for the whole run)
@@ -301,6 +305,8 @@ inline void Config::assign(const std::string& key, const std::string& raw0) {
       incoherent_dm_offsets.push_back(Expr::eval(p));
   }
   else if (key == "incoherent_output_path") incoherent_output_path = raw;
+  else if (key == "incoherent_normalize") incoherent_normalize = B();
+  else if (key == "incoherent_normalize_blocks") incoherent_normalize_blocks = I();
   else if (key == "filterbank_output_path") filterbank_output_path = raw;
   else if (key == "filterbank_tscrunch") filterbank_tscrunch = I();
   else if (key == "filterbank_fscrunch") filterbank_fscrunch = I();
@@ -409,6 +415,10 @@ inline std::string Config::dump() const {
       o << (i ? "," : "") << incoherent_dm_offsets[i];
     o << "\n"
       << "incoherent_output_path = " << incoherent_output_path << "\n";
+    if (incoherent_normalize)
+      o << "incoherent_normalize = 1\n"
+        << "incoherent_normalize_blocks = " << incoherent_normalize_blocks
+        << "\n";
   }
   if (!fold_output_path.empty()) {
     const auto prec = o.precision(17);

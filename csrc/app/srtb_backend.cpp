@@ -207,9 +207,19 @@ int main(int argc, char** argv) {
   // incoherent DM-offset search (incoherent_dm_offsets): it consumes the
   // per-stream power plane, with or without a filterbank file
   const bool incoh_mode = !cfg.incoherent_dm_offsets.empty();
+  if (cfg.incoherent_normalize_blocks < 1 ||
+      cfg.incoherent_normalize_blocks > srtb_hip::kIncohNormMaxBlocks) {
+    SRTB_APP_LOGE("config: incoherent_normalize_blocks must be 1 .. "
+                  << srtb_hip::kIncohNormMaxBlocks);
+    return 2;
+  }
   if (incoh_mode != !cfg.incoherent_output_path.empty()) {
     SRTB_APP_LOGE("config: incoherent_dm_offsets and incoherent_output_path "
                   "need each other");
+    return 2;
+  }
+  if (cfg.incoherent_normalize && !incoh_mode) {
+    SRTB_APP_LOGE("config: incoherent_normalize needs incoherent_dm_offsets");
     return 2;
   }
   if (incoh_mode && trial_mode) {
@@ -690,6 +700,8 @@ int main(int argc, char** argv) {
     ic.offsets = cfg.incoherent_dm_offsets;
     ic.snr_threshold = cfg.signal_detect_signal_noise_threshold;
     ic.max_boxcar = cfg.signal_detect_max_boxcar_length;
+    ic.normalize = cfg.incoherent_normalize;
+    ic.normalize_blocks = cfg.incoherent_normalize_blocks;
     incoh_tsamp = ic.tsamp;
     for (int si = 0; si < n_streams; ++si) {
       try {
@@ -713,7 +725,8 @@ int main(int argc, char** argv) {
       SRTB_APP_LOGI("incoherent search -> " << path << " ("
                     << ic.offsets.size() << " offsets, D_max = "
                     << searchers.back()->d_max() << " rows of " << ic.rows
-                    << " per block)");
+                    << " per block"
+                    << (ic.normalize ? ", channels normalised" : "") << ")");
     }
   }
 

@@ -1452,14 +1452,86 @@ std::vector<torch::Tensor> t_incoh_detect(torch::Tensor Y, double snr,
   return {peak, index.to(torch::kInt64), rms, count.to(torch::kInt64), mu};
 }
 
+// One step of the normalisation state on a block plane [R][C]: M, V (float64
+// [C]) and G (float32 [C]) are updated in place; returns the live count.
+int64_t t_incoh_norm_update(torch::Tensor plane, double alpha,
+                            torch::Tensor M, torch::Tensor V,
+                            torch::Tensor G) {
+  for (const torch::Tensor& t : {plane, M, V, G}) {
+    CHECK_CUDA(t);
+    CHECK_CONTIG(t);
+  }
+  TORCH_CHECK(plane.scalar_type() == torch::kFloat32 && plane.dim() == 2 &&
+                  plane.size(0) >= 1 && plane.size(1) >= 1,
+              "incoh_norm_update: plane must be float32 [R][C], R, C >= 1");
+  const int64_t R = plane.size(0), C = plane.size(1);
+  TORCH_CHECK(M.scalar_type() == torch::kFloat64 &&
+                  V.scalar_type() == torch::kFloat64 && M.dim() == 1 &&
+                  V.dim() == 1 && M.size(0) == C && V.size(0) == C,
+              "incoh_norm_update: M and V must be float64 [C]");
+  TORCH_CHECK(G.scalar_type() == torch::kFloat32 && G.dim() == 1 &&
+                  G.size(0) == C,
+              "incoh_norm_update: G must be float32 [C]");
+  TORCH_CHECK(plane.device() == M.device() && M.device() == V.device() &&
+                  V.device() == G.device(),
+              "incoh_norm_update: tensors on different devices");
+  TORCH_CHECK(alpha > 0.0 && alpha <= 1.0,
+              "incoh_norm_update: alpha must be in (0, 1]");
+  auto partials = torch::empty({(int64_t)incoh_norm_partials(C)},
+                               plane.options().dtype(torch::kFloat64));
+  auto live = torch::empty({1}, plane.options().dtype(torch::kInt32));
+  check(incoh_norm_update(plane.data_ptr<float>(), R, C, alpha,
+                          partials.data_ptr<double>(), M.data_ptr<double>(),
+                          V.data_ptr<double>(), G.data_ptr<float>(),
+                          reinterpret_cast<unsigned*>(live.data_ptr<int>()),
+                          cur_stream()),
+        "incoh_norm_update");
+  return live.item<int64_t>();
+}
+
+// ring[(write_row + r) mod rows] = (plane[r] - (float)M) * G, in place
+void t_incoh_norm_apply(torch::Tensor plane, torch::Tensor M, torch::Tensor G,
+                        torch::Tensor ring, int64_t write_row) {
+  for (const torch::Tensor& t : {plane, M, G, ring}) {
+    CHECK_CUDA(t);
+    CHECK_CONTIG(t);
+  }
+  TORCH_CHECK(plane.scalar_type() == torch::kFloat32 && plane.dim() == 2 &&
+                  plane.size(0) >= 1 && plane.size(1) >= 1,
+              "incoh_norm_apply: plane must be float32 [R][C], R, C >= 1");
+  const int64_t R = plane.size(0), C = plane.size(1);
+  TORCH_CHECK(M.scalar_type() == torch::kFloat64 && M.dim() == 1 &&
+                  M.size(0) == C,
+              "incoh_norm_apply: M must be float64 [C]");
+  TORCH_CHECK(G.scalar_type() == torch::kFloat32 && G.dim() == 1 &&
+                  G.size(0) == C,
+              "incoh_norm_apply: G must be float32 [C]");
+  TORCH_CHECK(ring.scalar_type() == torch::kFloat32 && ring.dim() == 2 &&
+                  ring.size(1) == C && ring.size(0) >= R,
+              "incoh_norm_apply: ring must be float32 [rows >= R][C]");
+  TORCH_CHECK(write_row >= 0 && write_row < ring.size(0),
+              "incoh_norm_apply: write_row must be in 0 .. rows - 1");
+  TORCH_CHECK(plane.device() == M.device() && M.device() == G.device() &&
+                  G.device() == ring.device(),
+              "incoh_norm_apply: tensors on different devices");
+  check(incoh_norm_apply(plane.data_ptr<float>(), R, C, M.data_ptr<double>(),
+                         G.data_ptr<float>(), ring.data_ptr<float>(),
+                         ring.size(0), write_row, cur_stream()),
+        "incoh_norm_apply");
+}
+
 class PyIncoherentSearch {
  public:
   PyIncoherentSearch(int64_t rows, int64_t channels, double fch1, double foff,
                      double tsamp, std::vector<double> offsets,
                      double snr_threshold, int64_t max_boxcar,
-                     int64_t n_slots) {
+                     int64_t n_slots, bool normalize,
+                     int64_t normalize_blocks) {
     TORCH_CHECK(rows >= 0 && channels >= 0 && max_boxcar >= 0,
                 "IncoherentSearch: sizes must not be negative");
+    TORCH_CHECK(normalize_blocks >= 0,
+                "IncoherentSearch: normalize_blocks must be 1 .. ",
+                kIncohNormMaxBlocks);
     IncoherentSearchConfig c;
     c.rows = (size_t)rows;
     c.channels = (size_t)channels;
@@ -1469,6 +1541,8 @@ class PyIncoherentSearch {
     c.offsets = std::move(offsets);
     c.snr_threshold = snr_threshold;
     c.max_boxcar = (size_t)max_boxcar;
+    c.normalize = normalize;
+    c.normalize_blocks = (size_t)normalize_blocks;
     s_ = std::make_unique<IncoherentSearch>(c, (int)n_slots);
     check(hipEventCreateWithFlags(&ev_, hipEventDisableTiming),
           "incoherent producer event");
@@ -1496,7 +1570,7 @@ class PyIncoherentSearch {
     return s_->submit_plane(plane.data_ptr<float>(), ev_);
   }
 
-  // {valid, first_row, block, trials: [{offset, mean, lengths:
+  // {valid, first_row, block, live_channels, trials: [{offset, mean, lengths:
   // [{boxcar_length, peak, index, rms, count, snr}]}]}
   py::dict wait(int64_t k) {
     const IncoherentResult r = s_->wait((int)k);
@@ -1504,6 +1578,7 @@ class PyIncoherentSearch {
     d["valid"] = r.valid;
     d["first_row"] = r.first_row;
     d["block"] = r.block;
+    d["live_channels"] = r.live_channels;
     py::list trials;
     for (const IncoherentTrial& t : r.trials) {
       py::dict td;
@@ -1544,6 +1619,12 @@ class PyIncoherentSearch {
         .clone();
   }
 
+  // the normalisation's running state, [C], copied once everything submitted
+  // so far has run
+  torch::Tensor norm_mean() { return norm_state(s_->norm_mean()); }
+  torch::Tensor norm_var() { return norm_state(s_->norm_var()); }
+  torch::Tensor norm_gain() { return norm_state(s_->norm_gain()); }
+
   void reset() { s_->reset(); }
   int64_t d_max() const { return (int64_t)s_->d_max(); }
   int64_t rows() const { return (int64_t)s_->rows(); }
@@ -1551,6 +1632,20 @@ class PyIncoherentSearch {
   int64_t trials() const { return (int64_t)s_->trials(); }
 
  private:
+  template <typename T>
+  torch::Tensor norm_state(const T* dev) {
+    TORCH_CHECK(s_->normalize(),
+                "IncoherentSearch: built without normalize, no state");
+    check(hipStreamSynchronize(s_->stream()), "incoherent stream sync");
+    auto out = torch::empty(
+        {(int64_t)s_->channels()},
+        torch::TensorOptions().dtype(c10::CppTypeToScalarType<T>::value));
+    check(hipMemcpy(out.data_ptr(), dev, s_->channels() * sizeof(T),
+                    hipMemcpyDeviceToHost),
+          "incoherent state d2h");
+    return out;
+  }
+
   std::unique_ptr<IncoherentSearch> s_;
   hipEvent_t ev_ = nullptr;
 };
@@ -1711,15 +1806,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("delays"), py::arg("R"));
   m.def("incoh_detect", &t_incoh_detect, py::arg("Y"), py::arg("snr"),
         py::arg("max_boxcar"));
+  m.def("incoh_norm_update", &t_incoh_norm_update, py::arg("plane"),
+        py::arg("alpha"), py::arg("M"), py::arg("V"), py::arg("G"));
+  m.def("incoh_norm_apply", &t_incoh_norm_apply, py::arg("plane"),
+        py::arg("M"), py::arg("G"), py::arg("ring"), py::arg("write_row"));
   m.attr("INCOH_CHANNEL_CHUNK") = (int64_t)kIncohChannelChunk;
   m.attr("INCOH_MAX_ROWS") = (int64_t)kIncohMaxRows;
   py::class_<PyIncoherentSearch>(m, "IncoherentSearch")
       .def(py::init<int64_t, int64_t, double, double, double,
-                    std::vector<double>, double, int64_t, int64_t>(),
+                    std::vector<double>, double, int64_t, int64_t, bool,
+                    int64_t>(),
            py::arg("rows"), py::arg("channels"), py::arg("fch1"),
            py::arg("foff"), py::arg("tsamp"), py::arg("offsets"),
            py::arg("snr_threshold"), py::arg("max_boxcar"),
-           py::arg("n_slots") = 2)
+           py::arg("n_slots") = 2, py::arg("normalize") = false,
+           py::arg("normalize_blocks") = 8)
       .def("submit", &PyIncoherentSearch::submit, py::arg("engine"),
            py::arg("slot"))
       .def("submit_plane", &PyIncoherentSearch::submit_plane, py::arg("plane"))
@@ -1727,6 +1828,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("plane", &PyIncoherentSearch::plane)
       .def("delays", &PyIncoherentSearch::delays)
       .def("reset", &PyIncoherentSearch::reset)
+      .def("norm_mean", &PyIncoherentSearch::norm_mean)
+      .def("norm_var", &PyIncoherentSearch::norm_var)
+      .def("norm_gain", &PyIncoherentSearch::norm_gain)
       .def_property_readonly("d_max", &PyIncoherentSearch::d_max)
       .def_property_readonly("rows", &PyIncoherentSearch::rows)
       .def_property_readonly("channels", &PyIncoherentSearch::channels)

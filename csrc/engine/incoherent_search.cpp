@@ -66,6 +66,9 @@ IncoherentSearch::IncoherentSearch(const IncoherentSearchConfig& cfg,
   if (C < 1) throw std::runtime_error("incoherent search: needs channels >= 1");
   if (cfg.max_boxcar < 1)
     throw std::runtime_error("incoherent search: max_boxcar must be >= 1");
+  if (cfg.normalize_blocks < 1 || cfg.normalize_blocks > kIncohNormMaxBlocks)
+    throw std::runtime_error("incoherent search: normalize_blocks must be "
+                             "1 .. " + std::to_string(kIncohNormMaxBlocks));
   nl_ = incoh_lengths(cfg.max_boxcar);
   delays_ = incoherent_delays(cfg.fch1, cfg.foff, C, cfg.tsamp, cfg.offsets);
   for (int32_t d : delays_)
@@ -90,19 +93,30 @@ IncoherentSearch::IncoherentSearch(const IncoherentSearchConfig& cfg,
   if (const size_t np = incoh_partials(T, R, C))
     check_hip(hipMalloc(&partials_, np * sizeof(float)),
               "incoherent partials alloc");
+  if (cfg.normalize) {
+    check_hip(hipMalloc(&norm_m_, 2 * C * sizeof(double)),
+              "incoherent normalisation alloc");
+    norm_v_ = norm_m_ + C;
+    check_hip(hipMalloc(&norm_g_, C * sizeof(float)),
+              "incoherent normalisation alloc");
+    check_hip(hipMalloc(&norm_partials_,
+                        incoh_norm_partials(C) * sizeof(double)),
+              "incoherent normalisation alloc");
+  }
   const size_t tl = T * (size_t)nl_;
+  const size_t n_u32 = 2 * tl + (cfg.normalize ? 1 : 0);
   slots_.resize(n_slots);
   for (Slot& s : slots_) {
     check_hip(hipMalloc(&s.y, T * R * sizeof(float)), "incoherent plane alloc");
     check_hip(hipMalloc(&s.res_f64, (2 * tl + T) * sizeof(double)),
               "incoherent result alloc");
-    check_hip(hipMalloc(&s.res_u32, 2 * tl * sizeof(unsigned)),
+    check_hip(hipMalloc(&s.res_u32, n_u32 * sizeof(unsigned)),
               "incoherent result alloc");
     check_hip(hipHostMalloc(&s.h_y, T * R * sizeof(float)),
               "pinned incoherent plane");
     check_hip(hipHostMalloc(&s.h_f64, (2 * tl + T) * sizeof(double)),
               "pinned incoherent result");
-    check_hip(hipHostMalloc(&s.h_u32, 2 * tl * sizeof(unsigned)),
+    check_hip(hipHostMalloc(&s.h_u32, n_u32 * sizeof(unsigned)),
               "pinned incoherent result");
     for (hipEvent_t* e : {&s.ready, &s.done})
       check_hip(hipEventCreateWithFlags(e, hipEventDisableTiming),
@@ -126,6 +140,9 @@ IncoherentSearch::~IncoherentSearch() {
   if (ring_) (void)hipFree(ring_);
   if (d_delays_) (void)hipFree(d_delays_);
   if (partials_) (void)hipFree(partials_);
+  if (norm_m_) (void)hipFree(norm_m_);
+  if (norm_g_) (void)hipFree(norm_g_);
+  if (norm_partials_) (void)hipFree(norm_partials_);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -135,6 +152,14 @@ void IncoherentSearch::reset() {
                            ring_rows_ * cfg_.channels * sizeof(float),
                            stream_),
             "incoherent reset");
+  if (cfg_.normalize) {
+    check_hip(hipMemsetAsync(norm_m_, 0, 2 * cfg_.channels * sizeof(double),
+                             stream_),
+              "incoherent reset");
+    check_hip(hipMemsetAsync(norm_g_, 0, cfg_.channels * sizeof(float),
+                             stream_),
+              "incoherent reset");
+  }
   write_row_ = 0;
   block_ = 0;
 }
@@ -163,17 +188,32 @@ int IncoherentSearch::submit_plane(const float* dev_plane, hipEvent_t ready) {
   const size_t T = cfg_.offsets.size(), R = cfg_.rows, C = cfg_.channels;
 
   if (ready) check_hip(hipStreamWaitEvent(stream_, ready, 0), "incoherent wait");
+  const size_t tl = T * (size_t)nl_;
   // the block's R rows go to ring rows write_row_ ..., wrapping at most once
-  const size_t first = std::min(R, ring_rows_ - write_row_);
-  check_hip(hipMemcpyAsync(ring_ + write_row_ * C, dev_plane,
-                           first * C * sizeof(float),
-                           hipMemcpyDeviceToDevice, stream_),
-            "incoherent history");
-  if (first < R)
-    check_hip(hipMemcpyAsync(ring_, dev_plane + first * C,
-                             (R - first) * C * sizeof(float),
+  if (cfg_.normalize) {
+    // the state that normalises block b includes block b
+    const uint64_t seen = block_ + 1;
+    const double alpha =
+        1.0 / (double)std::min<uint64_t>(seen, cfg_.normalize_blocks);
+    check_hip(incoh_norm_update(dev_plane, R, C, alpha, norm_partials_,
+                                norm_m_, norm_v_, norm_g_, s.res_u32 + 2 * tl,
+                                stream_),
+              "incoherent normalisation");
+    check_hip(incoh_norm_apply(dev_plane, R, C, norm_m_, norm_g_, ring_,
+                               ring_rows_, write_row_, stream_),
+              "incoherent normalisation");
+  } else {
+    const size_t first = std::min(R, ring_rows_ - write_row_);
+    check_hip(hipMemcpyAsync(ring_ + write_row_ * C, dev_plane,
+                             first * C * sizeof(float),
                              hipMemcpyDeviceToDevice, stream_),
               "incoherent history");
+    if (first < R)
+      check_hip(hipMemcpyAsync(ring_, dev_plane + first * C,
+                               (R - first) * C * sizeof(float),
+                               hipMemcpyDeviceToDevice, stream_),
+                "incoherent history");
+  }
   write_row_ = (write_row_ + R) % ring_rows_;
   // the ring holds exactly D_max + R rows: the oldest, global row
   // block * R - D_max, follows the newest
@@ -184,7 +224,6 @@ int IncoherentSearch::submit_plane(const float* dev_plane, hipEvent_t ready) {
   s.valid = block_ * R >= d_max_;
   s.first_row = (int64_t)(block_ * R) - (int64_t)d_max_;
   ++block_;
-  const size_t tl = T * (size_t)nl_;
   if (s.valid) {
     check_hip(incoh_detect(s.y, T, R, nl_, cfg_.snr_threshold, s.res_f64,
                            s.res_u32, s.res_f64 + tl, s.res_u32 + tl,
@@ -193,8 +232,15 @@ int IncoherentSearch::submit_plane(const float* dev_plane, hipEvent_t ready) {
     check_hip(hipMemcpyAsync(s.h_f64, s.res_f64, (2 * tl + T) * sizeof(double),
                              hipMemcpyDeviceToHost, stream_),
               "incoherent result d2h");
-    check_hip(hipMemcpyAsync(s.h_u32, s.res_u32, 2 * tl * sizeof(unsigned),
+    // with normalize, the live count rides behind the counts
+    check_hip(hipMemcpyAsync(s.h_u32, s.res_u32,
+                             (2 * tl + (cfg_.normalize ? 1 : 0)) *
+                                 sizeof(unsigned),
                              hipMemcpyDeviceToHost, stream_),
+              "incoherent result d2h");
+  } else if (cfg_.normalize) {
+    check_hip(hipMemcpyAsync(s.h_u32 + 2 * tl, s.res_u32 + 2 * tl,
+                             sizeof(unsigned), hipMemcpyDeviceToHost, stream_),
               "incoherent result d2h");
   }
   check_hip(hipMemcpyAsync(s.h_y, s.y, T * R * sizeof(float),
@@ -213,8 +259,9 @@ IncoherentResult IncoherentSearch::wait(int k) {
   r.valid = s.valid;
   r.first_row = s.first_row;
   r.block = s.block;
-  if (!s.valid) return r;
   const size_t T = cfg_.offsets.size(), tl = T * (size_t)nl_;
+  if (cfg_.normalize) r.live_channels = s.h_u32[2 * tl];
+  if (!s.valid) return r;
   r.trials.resize(T);
   for (size_t t = 0; t < T; ++t) {
     IncoherentTrial& tr = r.trials[t];

@@ -33,6 +33,10 @@ struct IncoherentSearchConfig {
   std::vector<double> offsets;  // delta_t, pc cm^-3, either sign
   double snr_threshold = 6.0;
   size_t max_boxcar = 1;
+  // per-channel normalisation of the rows entering the history, by a running
+  // mean and deviation over about normalize_blocks blocks (1 .. 65536)
+  bool normalize = false;
+  size_t normalize_blocks = 8;
 };
 
 // d[t][c] of the definition, built in fp64; throws on non-finite input
@@ -59,6 +63,9 @@ struct IncoherentResult {
   bool valid = false;     // block * R >= D_max; trials is empty otherwise
   int64_t first_row = 0;  // global row of Y[.][0] = block * R - D_max
   uint64_t block = 0;     // ordinal since construction / reset()
+  // channels with a gain > 0 in this block, valid or not (0 with
+  // normalize off)
+  uint32_t live_channels = 0;
   std::vector<IncoherentTrial> trials;
 };
 
@@ -81,7 +88,8 @@ class IncoherentSearch {
   // One hipEventSynchronize on the slot's `done` event.
   IncoherentResult wait(int k);
 
-  // Zeroes the history and restarts priming (after dropped blocks).
+  // Zeroes the history and the normalisation state and restarts priming
+  // (after dropped blocks).
   void reset();
 
   size_t rows() const { return cfg_.rows; }
@@ -94,12 +102,20 @@ class IncoherentSearch {
   const std::vector<double>& offsets() const { return cfg_.offsets; }
   float* plane_ptr(int k) const;         // device Y [T][R]
   const float* plane_host(int k) const;  // pinned mirror, after wait(k)
+  // The running state of the normalisation, device [C]; null with normalize
+  // off.  Written on stream(): synchronize it before reading.
+  bool normalize() const { return cfg_.normalize; }
+  const double* norm_mean() const { return norm_m_; }
+  const double* norm_var() const { return norm_v_; }
+  const float* norm_gain() const { return norm_g_; }
+  hipStream_t stream() const { return stream_; }
 
  private:
   struct Slot {
     float* y = nullptr;        // [T][R]
     double* res_f64 = nullptr;  // peak [T][NL], rms [T][NL], mu [T]
-    unsigned* res_u32 = nullptr;  // index [T][NL], count [T][NL]
+    // index [T][NL], count [T][NL]; with normalize, live [1] after them
+    unsigned* res_u32 = nullptr;
     float* h_y = nullptr;
     double* h_f64 = nullptr;
     unsigned* h_u32 = nullptr;
@@ -116,6 +132,12 @@ class IncoherentSearch {
   float* ring_ = nullptr;      // [D_max + R][C]
   int* d_delays_ = nullptr;    // [T][C]
   float* partials_ = nullptr;  // shared: the one stream serializes the blocks
+  // normalisation (allocated with cfg_.normalize only): running mean and
+  // variance, gain, scratch of the block statistics
+  double* norm_m_ = nullptr;   // [C], norm_v_ follows it in one allocation
+  double* norm_v_ = nullptr;   // [C]
+  float* norm_g_ = nullptr;    // [C]
+  double* norm_partials_ = nullptr;
   hipStream_t stream_ = nullptr;
   std::vector<Slot> slots_;
   int next_slot_ = 0;

@@ -348,6 +348,38 @@ hipError_t incoh_detect(const float* Y, size_t T, size_t R, int n_lengths,
                         double* out_rms, unsigned* out_count, double* out_mu,
                         hipStream_t stream);
 
+// Per-channel normalisation of a block before it enters the history
+// (docs/ARCHITECTURE.md, "Per-channel normalisation").
+constexpr size_t kIncohNormMaxBlocks = 65536;  // K of the running average
+
+// Block statistics of plane[R][C] and one step of the running state, all
+// fp64: with x0 = plane[0][c], s = sum_r (x - x0), s2 = sum_r (x - x0)^2
+// (row chunks summed in chunk order, a fixed number of them),
+//   m = x0 + s / R,   v = max(s2 / R - (s / R)^2, 0)
+//   M[c] += alpha * (m - M[c]),   V[c] += alpha * (v - V[c])
+// every operation rounded on its own, then G[c] = (float)(1 / sqrt(V[c]))
+// where V[c] > 0, else 0, and *live = #{c : G[c] > 0}.  M, V, G are updated in
+// place.  partials: device scratch of incoh_norm_partials(C) doubles.  The
+// order of summation depends on R, C and launch constants only; no atomics.
+// R == 0, C == 0 or a null pointer returns hipErrorInvalidValue and launches
+// nothing.
+size_t incoh_norm_partials(size_t C);
+hipError_t incoh_norm_update(const float* plane, size_t R, size_t C,
+                             double alpha, double* partials, double* M,
+                             double* V, float* G, unsigned* live,
+                             hipStream_t stream);
+
+// ring[(write_row + r) mod ring_rows][c] = (plane[r][c] - (float)M[c]) * G[c],
+// r < R: one fp32 subtraction and one fp32 multiplication, each rounded on its
+// own.  16-byte accesses where C % 4 == 0 and plane, ring and G are 16-byte
+// aligned, scalar ones otherwise, with the same bits.  The other ring rows are
+// not touched.  R == 0, C == 0, ring_rows < R, write_row >= ring_rows or a
+// null pointer returns hipErrorInvalidValue and launches nothing.
+hipError_t incoh_norm_apply(const float* plane, size_t R, size_t C,
+                            const double* M, const float* G, float* ring,
+                            size_t ring_rows, size_t write_row,
+                            hipStream_t stream);
+
 // ---------------- hand-written Stockham FFT ----------------
 // One generic pass of the LDS-staged Stockham FFT (csrc/kernels/fft.hip).
 // Index-math oracle: srtb_amd/fftref.py.  Host-side planning:

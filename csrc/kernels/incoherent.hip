@@ -19,6 +19,12 @@
 // of the 160 KiB of a gfx950 CU, which leaves such a workgroup the CU to
 // itself); every boxcar length then takes two passes over it, sum of squares
 // + ordered maximum, and the count above the threshold.
+//
+// incoh_norm_update / incoh_norm_apply: the optional per-channel
+// normalisation of the rows on their way into the history ring.  update reads
+// the block's [R][C] plane once for the fp64 block statistics (row chunks in
+// fixed order) and advances the running mean, variance and gain; apply writes
+// (x - mean) * gain into the ring in place of the device-to-device copy.
 
 #include "../include/srtb_kernels.h"
 #include "common.h"
@@ -266,6 +272,131 @@ k_incoh_detect(const float* __restrict__ Y, size_t R, int n_lengths,
   if (tid == 0) out_mu[t] = mu;
 }
 
+// ---- per-channel normalisation ----
+
+constexpr int kIncohNormChunks = 64;      // row chunks of the block statistics
+constexpr int kIncohNormRowsPerThread = 8;  // rows a thread of apply walks
+
+// a * b rounded on its own.  The build contracts a * b + c across statements
+// and ignores the contract pragma; an fma with a zero addend is one rounding
+// of the product and is not merged into the addition that follows.
+__device__ __forceinline__ double mul_rn(double a, double b) {
+  return __builtin_fma(a, b, 0.0);
+}
+
+// grid: x = 256 channels, y = row chunk.  Lanes run along c, so a wave's load
+// of a row is one contiguous run.  partials: [chunks][2][C]; a chunk past the
+// last row writes zeros.
+__global__ void __launch_bounds__(kBlock)
+k_incoh_norm_partial(const float* __restrict__ P, size_t R, size_t C,
+                     int n_chunks, double* __restrict__ partials) {
+  const size_t c = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= C) return;
+  const int chunk = blockIdx.y;
+  const size_t rows_per = (R + n_chunks - 1) / n_chunks;
+  const size_t r0 = min((size_t)chunk * rows_per, R);
+  const size_t r1 = min(r0 + rows_per, R);
+  const double x0 = (double)P[c];
+  double s = 0.0, s2 = 0.0;
+#pragma unroll 8
+  for (size_t r = r0; r < r1; ++r) {
+    const double d = (double)P[r * C + c] - x0;
+    s += d;
+    s2 += mul_rn(d, d);
+  }
+  partials[((size_t)chunk * 2 + 0) * C + c] = s;
+  partials[((size_t)chunk * 2 + 1) * C + c] = s2;
+}
+
+// one thread per channel: the chunks in chunk order, then the running state
+__global__ void __launch_bounds__(kBlock)
+k_incoh_norm_state(const float* __restrict__ P, size_t R, size_t C,
+                   int n_chunks, const double* __restrict__ partials,
+                   double alpha, double* __restrict__ M,
+                   double* __restrict__ V, float* __restrict__ G) {
+  const size_t c = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= C) return;
+  double s = 0.0, s2 = 0.0;
+  for (int k = 0; k < n_chunks; ++k) {
+    s += partials[((size_t)k * 2 + 0) * C + c];
+    s2 += partials[((size_t)k * 2 + 1) * C + c];
+  }
+  const double ds = s / (double)R;  // mean of x - x0
+  const double m = (double)P[c] + ds;
+  double v = s2 / (double)R - mul_rn(ds, ds);
+  v = v > 0.0 ? v : 0.0;
+  const double m_run = M[c], v_run = V[c];
+  const double m_new = m_run + mul_rn(alpha, m - m_run);
+  const double v_new = v_run + mul_rn(alpha, v - v_run);
+  M[c] = m_new;
+  V[c] = v_new;
+  G[c] = v_new > 0.0 ? (float)(1.0 / sqrt(v_new)) : 0.0f;
+}
+
+// one workgroup: #{G > 0}, a fixed shuffle tree per wave, the waves in order
+__global__ void __launch_bounds__(kBlock)
+k_incoh_norm_live(const float* __restrict__ G, size_t C,
+                  unsigned* __restrict__ live) {
+  __shared__ unsigned per_wave[kBlock / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned n = 0;
+  for (size_t c = threadIdx.x; c < C; c += kBlock) n += G[c] > 0.0f ? 1u : 0u;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off, 64);
+  if (lane == 0) per_wave[wave] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned total = 0;
+    for (int w = 0; w < kBlock / 64; ++w) total += per_wave[w];
+    *live = total;
+  }
+}
+
+__device__ __forceinline__ float norm1(float x, float m, float g) {
+  // a subtraction, then a multiplication: nothing here can contract
+  return (x - m) * g;
+}
+
+// grid: x = 256 lanes of channels (4 adjacent ones per lane with VEC4), y =
+// kIncohNormRowsPerThread rows.  A thread keeps (float)M and G of its channels
+// in registers over its rows.  Block row r goes to ring row
+// (write_row + r) mod ring_rows.
+template <bool VEC4>
+__global__ void __launch_bounds__(kBlock)
+k_incoh_norm_apply(const float* __restrict__ P, size_t R, size_t C,
+                   const double* __restrict__ M, const float* __restrict__ G,
+                   float* __restrict__ ring, size_t ring_rows,
+                   size_t write_row) {
+  const size_t c = ((size_t)blockIdx.x * kBlock + threadIdx.x) * (VEC4 ? 4 : 1);
+  if (c >= C) return;
+  const size_t r0 = (size_t)blockIdx.y * kIncohNormRowsPerThread;
+  const size_t r1 = min(r0 + kIncohNormRowsPerThread, R);
+  if (VEC4) {
+    // C is a multiple of 4: c + 3 < C
+    const float4 g = *reinterpret_cast<const float4*>(G + c);
+    const float m0 = (float)M[c], m1 = (float)M[c + 1], m2 = (float)M[c + 2],
+                m3 = (float)M[c + 3];
+    for (size_t r = r0; r < r1; ++r) {
+      const float4 x = *reinterpret_cast<const float4*>(P + r * C + c);
+      size_t w = write_row + r;
+      if (w >= ring_rows) w -= ring_rows;
+      float4 y;
+      y.x = norm1(x.x, m0, g.x);
+      y.y = norm1(x.y, m1, g.y);
+      y.z = norm1(x.z, m2, g.z);
+      y.w = norm1(x.w, m3, g.w);
+      *reinterpret_cast<float4*>(ring + w * C + c) = y;
+    }
+  } else {
+    const float g = G[c], m = (float)M[c];
+    for (size_t r = r0; r < r1; ++r) {
+      size_t w = write_row + r;
+      if (w >= ring_rows) w -= ring_rows;
+      ring[w * C + c] = norm1(P[r * C + c], m, g);
+    }
+  }
+}
+
 }  // namespace
 
 int incoh_chunks(size_t C) {
@@ -331,6 +462,61 @@ hipError_t incoh_detect(const float* Y, size_t T, size_t R, int n_lengths,
   hipLaunchKernelGGL(k_incoh_detect, dim3((uint32_t)T), dim3(kDetectBlock),
                      lds, stream, Y, R, n_lengths, snr, out_peak, out_index,
                      out_rms, out_count, out_mu);
+  SRTB_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+size_t incoh_norm_partials(size_t C) {
+  return (size_t)kIncohNormChunks * 2 * C;
+}
+
+hipError_t incoh_norm_update(const float* plane, size_t R, size_t C,
+                             double alpha, double* partials, double* M,
+                             double* V, float* G, unsigned* live,
+                             hipStream_t stream) {
+  if (R == 0 || C == 0 || !plane || !partials || !M || !V || !G || !live)
+    return hipErrorInvalidValue;
+  const size_t gx = (C + kBlock - 1) / kBlock;
+  if (gx >= (1ull << 31)) return hipErrorInvalidValue;
+  const int chunks = (int)(R < (size_t)kIncohNormChunks ? R : kIncohNormChunks);
+  hipLaunchKernelGGL(k_incoh_norm_partial,
+                     dim3((uint32_t)gx, (uint32_t)chunks), dim3(kBlock), 0,
+                     stream, plane, R, C, chunks, partials);
+  hipLaunchKernelGGL(k_incoh_norm_state, dim3((uint32_t)gx), dim3(kBlock), 0,
+                     stream, plane, R, C, chunks, partials, alpha, M, V, G);
+  hipLaunchKernelGGL(k_incoh_norm_live, dim3(1), dim3(kBlock), 0, stream, G,
+                     C, live);
+  SRTB_CHECK_LAUNCH();
+  return hipSuccess;
+}
+
+hipError_t incoh_norm_apply(const float* plane, size_t R, size_t C,
+                            const double* M, const float* G, float* ring,
+                            size_t ring_rows, size_t write_row,
+                            hipStream_t stream) {
+  if (R == 0 || C == 0 || ring_rows < R || write_row >= ring_rows || !plane ||
+      !M || !G || !ring)
+    return hipErrorInvalidValue;
+  const size_t tiles =
+      (R + kIncohNormRowsPerThread - 1) / kIncohNormRowsPerThread;
+  if (tiles > 65535) return hipErrorInvalidValue;
+  auto aligned16 = [](const void* p) {
+    return reinterpret_cast<uintptr_t>(p) % 16 == 0;
+  };
+  // 16-byte accesses need rows (of the block and of the ring) and a gain
+  // vector that start on 16 bytes
+  const bool vec4 =
+      C % 4 == 0 && aligned16(plane) && aligned16(ring) && aligned16(G);
+  const size_t lanes = vec4 ? C / 4 : C;
+  const size_t gx = (lanes + kBlock - 1) / kBlock;
+  if (gx >= (1ull << 31)) return hipErrorInvalidValue;
+  const dim3 grid((uint32_t)gx, (uint32_t)tiles);
+  if (vec4)
+    hipLaunchKernelGGL(k_incoh_norm_apply<true>, grid, dim3(kBlock), 0, stream,
+                       plane, R, C, M, G, ring, ring_rows, write_row);
+  else
+    hipLaunchKernelGGL(k_incoh_norm_apply<false>, grid, dim3(kBlock), 0,
+                       stream, plane, R, C, M, G, ring, ring_rows, write_row);
   SRTB_CHECK_LAUNCH();
   return hipSuccess;
 }

@@ -69,6 +69,8 @@ _FIELD_KINDS = {
     "fold_subint_blocks": "int",
     "incoherent_dm_offsets": "reallist",
     "incoherent_output_path": "str",
+    "incoherent_normalize": "bool",
+    "incoherent_normalize_blocks": "int",
 }
 
 
@@ -137,6 +139,10 @@ class Config:
     # text file
     incoherent_dm_offsets: str = ""
     incoherent_output_path: str = ""
+    # per-channel normalisation of the rows before they are summed: off / on,
+    # and the blocks (1 .. 65536) the running mean and deviation average over
+    incoherent_normalize: bool = False
+    incoherent_normalize_blocks: int = 8
 
     # ---- assignment from strings (expression values) ----
 

@@ -115,10 +115,17 @@ def check_filterbank_polarization(cfg: Config, n_streams: int) -> None:
 
 def check_incoherent_config(cfg: Config) -> None:
     """Reject an incoherent_dm_offsets the run cannot honour."""
+    if not 1 <= cfg.incoherent_normalize_blocks <= ref.INCOH_NORM_MAX_BLOCKS:
+        raise SystemExit(
+            "config: incoherent_normalize_blocks must be 1 .. "
+            f"{ref.INCOH_NORM_MAX_BLOCKS}")
     if not cfg.incoherent_dm_offsets.strip():
         if cfg.incoherent_output_path:
             raise SystemExit(
                 "config: incoherent_output_path needs incoherent_dm_offsets")
+        if cfg.incoherent_normalize:
+            raise SystemExit(
+                "config: incoherent_normalize needs incoherent_dm_offsets")
         return
     if not cfg.incoherent_output_path:
         raise SystemExit(
@@ -159,6 +166,9 @@ class IncoherentOutput:
                   offsets=cfg.incoherent_offsets(),
                   snr_threshold=cfg.signal_detect_signal_noise_threshold,
                   max_boxcar=cfg.signal_detect_max_boxcar_length)
+        if cfg.incoherent_normalize:  # off: the searchers' own defaults
+            kw.update(normalize=True,
+                      normalize_blocks=cfg.incoherent_normalize_blocks)
         try:
             if native is not None:
                 self.searchers = [native.IncoherentSearch(

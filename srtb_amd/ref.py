@@ -829,14 +829,57 @@ def incoherent_result_trials(det: dict, offsets) -> list[dict]:
     return trials
 
 
+INCOH_NORM_MAX_BLOCKS = 65536
+
+
+def incoherent_norm_stats(P: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """(m, v) per channel of one block plane [R][C], float64: the mean and the
+    population variance, from the sums of x - x0 and (x - x0)^2 with
+    x0 = P[0][c], so a constant channel has exactly v = 0."""
+    P = np.asarray(P, dtype=np.float64)
+    if P.ndim != 2 or P.shape[0] < 1 or P.shape[1] < 1:
+        raise ValueError("incoherent_norm_stats: needs a plane [R][C]")
+    R = np.float64(P.shape[0])
+    d = P - P[0]
+    ds = d.sum(axis=0) / R
+    v = (d * d).sum(axis=0) / R - ds * ds
+    return P[0] + ds, np.maximum(v, 0.0)
+
+
+def incoherent_norm_gain(V: np.ndarray) -> np.ndarray:
+    """G = (float32)(1 / sqrt(V)) where V > 0, else 0."""
+    V = np.asarray(V, dtype=np.float64)
+    G = np.zeros(V.shape, dtype=np.float32)
+    live = V > 0
+    G[live] = (1.0 / np.sqrt(V[live])).astype(np.float32)
+    return G
+
+
+def incoherent_norm_apply(P: np.ndarray, M: np.ndarray,
+                          G: np.ndarray) -> np.ndarray:
+    """(P - (float32)M) * G in float32, each operation rounded on its own."""
+    P = np.asarray(P, dtype=np.float32)
+    m32 = np.asarray(M, dtype=np.float64).astype(np.float32)
+    return (P - m32[None, :]) * np.asarray(G, dtype=np.float32)[None, :]
+
+
 class CpuIncoherentSearch:
     """Streaming search with the history, priming and result semantics of the
     native IncoherentSearch: block b's output row j stands for global row
     b * R - D_max + j, rows before the stream are zero, and a block is valid
-    (and searched) iff b * R >= D_max."""
+    (and searched) iff b * R >= D_max.  With normalize, a block's rows enter
+    the history as (x - M) * G of the running per-channel state, which block
+    b updates with alpha = 1 / min(b + 1, normalize_blocks) before it is
+    applied to block b."""
 
     def __init__(self, R: int, C: int, fch1: float, foff: float, tsamp: float,
-                 offsets, snr_threshold: float, max_boxcar: int):
+                 offsets, snr_threshold: float, max_boxcar: int,
+                 normalize: bool = False, normalize_blocks: int = 8):
+        self.normalize = bool(normalize)
+        self.normalize_blocks = int(normalize_blocks)
+        if not 1 <= self.normalize_blocks <= INCOH_NORM_MAX_BLOCKS:
+            raise ValueError(f"incoherent search: normalize_blocks must be "
+                             f"1 .. {INCOH_NORM_MAX_BLOCKS}")
         self.offsets = [float(x) for x in np.atleast_1d(offsets)]
         if not 1 <= len(self.offsets) <= INCOH_MAX_TRIALS:
             raise ValueError(f"incoherent search: needs 1 .. "
@@ -861,15 +904,30 @@ class CpuIncoherentSearch:
     def reset(self) -> None:
         self.window = np.zeros((self.d_max + self.R, self.C), dtype=np.float64)
         self.block = 0
+        self.M = np.zeros(self.C, dtype=np.float64)
+        self.V = np.zeros(self.C, dtype=np.float64)
+        self.G = np.zeros(self.C, dtype=np.float32)
 
     def add(self, plane: np.ndarray) -> dict:
-        """One block's [R][C] plane -> {'valid', 'first_row', 'block', 'Y'
-        (float64 [T][R]), 'trials' (empty unless valid)}."""
+        """One block's [R][C] plane -> {'valid', 'first_row', 'block',
+        'live_channels' (0 unless normalize), 'Y' (float64 [T][R]), 'trials'
+        (empty unless valid)}."""
         plane = np.asarray(plane, dtype=np.float64)
         if plane.shape != (self.R, self.C):
             raise ValueError("incoherent search: plane shape differs")
-        self.window = np.concatenate([self.window[self.R:], plane])
         b = self.block
+        live = 0
+        if self.normalize:
+            alpha = np.float64(1.0) / np.float64(
+                min(b + 1, self.normalize_blocks))
+            m, v = incoherent_norm_stats(plane)
+            self.M = self.M + alpha * (m - self.M)
+            self.V = self.V + alpha * (v - self.V)
+            self.G = incoherent_norm_gain(self.V)
+            live = int((self.G > 0).sum())
+            plane = incoherent_norm_apply(plane, self.M, self.G).astype(
+                np.float64)
+        self.window = np.concatenate([self.window[self.R:], plane])
         self.block += 1
         Y = incoherent_dedisperse(self.window, self.delays, self.R)
         valid = b * self.R >= self.d_max
@@ -879,7 +937,7 @@ class CpuIncoherentSearch:
                 incoherent_detect(Y, self.snr_threshold, self.max_boxcar),
                 self.offsets)
         return {"valid": valid, "first_row": b * self.R - self.d_max,
-                "block": b, "Y": Y, "trials": trials}
+                "block": b, "live_channels": live, "Y": Y, "trials": trials}
 
 
 def incoherent_candidate_lines(result: dict, tsamp: float, dm: float) -> list[str]:
